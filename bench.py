@@ -15,10 +15,17 @@ TWO figures, both in the line:
 `--unbatched` makes the drop-in path the headline instead. Inputs are synthetic (dreamscene_amd/synth.py, SURVEY.md
 8d), resident in HBM before the timed region.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) including `roofline` for the dominant kernel (HIP events on
-the launch stream, via the library's GsrProfile; VALU issue fraction from the committed SQ counters) and `cpu_baseline`
-(the C port of the same algorithm on ALL host cores, the same on one thread, and the PyTorch-CPU oracle on all cores at
-C1 / C2; N=1 only).
+Prints ONE JSON line on rank 0. A plain run sets up, warms up, times `--steps` steps and
+prints the line (`value`, `ms_per_step`); the entries that take runs of their own are measured only with `--full`:
+`dropin_views_per_s`, `sustained`, `rotating_cameras`, `training_like`, `trainer_step`, `init_state`, `forward_only`,
+`roofline` for the dominant kernel (HIP events on the launch stream, via the library's GsrProfile; VALU issue fraction from
+the committed SQ counters), `exchange` / `rccl` (N > 1), and `cpu_baseline` with the oracle parity check (the C port of the
+same algorithm on ALL host cores, the same on one thread, and the PyTorch-CPU oracle on all cores at C1 / C2; N=1 only).
+Without `--full` those entries are null.
+
+`--dump-outputs DIR` writes what the last timed step computed (rank 0's views and the summed parameter gradients) as
+DIR/<name>.npy, float32, at most 64 MB in all (see write_outputs); the inputs are seeded, so two builds can be compared
+output for output.
 """
 from __future__ import annotations
 
@@ -123,7 +130,9 @@ def self_launch(n_gpus: int, argv) -> None:
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")      # dmabuf IPC: RCCL across processes needs it on this driver
     env.setdefault("OMP_NUM_THREADS", "8")
     sys.stdout.flush()
-    os.execve(sys.executable, self_launch_cmd(n_gpus, argv, port), env)
+    # a child process, not exec: this process has already opened the HIP runtime (device_count above)
+    import subprocess
+    sys.exit(subprocess.call(self_launch_cmd(n_gpus, argv, port), env=env))
 
 
 def main():
@@ -178,7 +187,18 @@ def main():
                          "DESIGN.md section 6 --, dense,rows under gloo)")
     ap.add_argument("--exchange-probe-steps", type=int, default=12,
                     help="--exchange measure: timed steps per wire format after the warm-up")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: drop-in, sustained, rotating-cameras, "
+                         "training-like, trainer-step, initial-state and forward-only legs, roofline, exchange / rccl figures, "
+                         "CPU baselines and the oracle parity check (the --no-* / --*-seconds options above select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:      # a plain run: set-up, warm-up, the timed steps, the line
+        args.no_cpu_baseline = args.no_dropin = args.no_roofline = True
+        args.sustain_seconds = args.rotate_seconds = args.train_seconds = 0.0
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         # `python bench.py --gpus N` without a launcher: become the launcher (one rank per GPU under torch.distributed.run);
@@ -300,6 +320,8 @@ def main():
         return outs[0], g2d[0]
 
     last_batched = [None]          # (outputs of all views, means2D gradients [V,P,3]) of the latest batched step
+    # (per-view outputs, per-view means2D gradients, per-view parameter gradients or None = in the arena) of the latest drop-in step
+    last_dropin = [None]
     plain_rasts = [GaussianRasterizer(raster_settings=s_) for s_ in settings_list]
     # the same modules with the opt-in internal streams (RasterContext.side_streams / GSR_SIDE_STREAMS=2: the forward of a call
     # whose inputs are provably unchanged since an earlier call runs on an internal stream beside the previous views)
@@ -321,24 +343,24 @@ def main():
                                   opacities=params["opacities"], scales=params["scales"],
                                   rotations=params["rotations"], cov3D_precomp=None)
             held.append((img, radii, da, means2D))
-        g2d0 = None
+        grads = []
         for img, radii, da, means2D in reversed(held):
-            gr = torch.autograd.grad([img, da], leaves + [means2D], [gi, gda])
-            g2d0 = gr[-1]
-        return held[0][:3], g2d0
+            grads.insert(0, torch.autograd.grad([img, da], leaves + [means2D], [gi, gda]))
+        last_dropin[0] = ([h[:3] for h in held], [g[-1] for g in grads], [g[:-1] for g in grads])
+        return held[0][:3], grads[0][-1]
 
     def step_dropin_arena():
-        out0 = g2d0 = None
-        for j, rast in enumerate(rasts):
+        held = []
+        for rast in rasts:
             means2D = torch.zeros_like(params["means3D"], requires_grad=True)
             img, radii, da = rast(means3D=params["means3D"], means2D=means2D, shs=params["shs"], colors_precomp=None,
                                   opacities=params["opacities"], scales=params["scales"],
                                   rotations=params["rotations"], cov3D_precomp=None)
             (g2d,) = torch.autograd.grad([img, da], [means2D], [gi, gda])
-            if j == 0:
-                out0, g2d0 = (img, radii, da), g2d
+            held.append((img, radii, da, g2d))
         reduce_grads()
-        return out0, g2d0
+        last_dropin[0] = ([h[:3] for h in held], [h[3] for h in held], None)
+        return held[0][:3], held[0][3]
 
     step = step_batched if batched else step_dropin
 
@@ -387,7 +409,8 @@ def main():
     # keeps the fastest; `rccl` = the plain in-place all-reduce of the REAL arena (236 P bytes at K = 16) on its own
     exchange_probe, rccl = None, None
     if world > 1:
-        rccl = measure_allreduce(arena, dev, backend, allreduce_scalars)
+        if args.full:
+            rccl = measure_allreduce(arena, dev, backend, allreduce_scalars)
         if args.exchange == "measure":
             # gloo (functional tests on one device) stages device tensors through the host for dense / rows only
             # (rows: the device form of round 6 -- self-describing messages, no host read: multiview._RowMessages)
@@ -449,8 +472,8 @@ def main():
         dominant = max(single, key=single.get)
         prof.reset()
         set_profile(None)
-        for _ in range(3):               # (back to the timed configuration: no event records, captured graphs replay)
-            step()
+    for _ in range(3):                   # (back to the timed configuration: no event records, captured graphs replay)
+        step()
 
     sync()
     host_stats.wait_s = 0.0
@@ -463,6 +486,9 @@ def main():
     elapsed = time.perf_counter() - t0
     if world > 1:
         elapsed = allreduce_scalars([elapsed], dist.ReduceOp.MAX)[0]
+    if args.dump_outputs and rank == 0:
+        outs_, m2d_, leaf_ = (*last_batched[0], None) if batched else last_dropin[0]
+        write_outputs(args.dump_outputs, last_step_outputs(outs_, m2d_, leaf_, arena))
 
     # ---- a longer window of the same step (the --steps region above is ~20 ms at the driver's K = 20)
     sustained = None
@@ -806,7 +832,7 @@ def main():
 
     # what the exchange would have to move for this rank's step (the arena holds the sum over the step's V views)
     exch = None
-    if exchange is not None:
+    if exchange is not None and args.full:
         skip_reduce[0] = True          # this rank's own step, before any exchange: the rows ITS views reached
         step() if batched else step_dropin_arena()      # (the plain per-view module does not write the arena)
         skip_reduce[0] = False
@@ -1003,7 +1029,7 @@ def main():
                        "capture_stats": dict(rast_captured.stats) if captured else None,
                        "dropin": ("`dropin_views_per_s`: the same views through one GaussianRasterizer call per view (the "
                                   f"reference's interface), {dropin['steps']} steps / {dropin['seconds']} s after the timed region") if dropin else
-                                 ("not measured (--no-dropin)" if batched else
+                                 (("not measured (--no-dropin)" if args.full else "not measured (without --full)") if batched else
                                   "`value` IS the drop-in figure (one GaussianRasterizer call per view)"),
                        "parallelism": f"{V} view(s)/GPU/step x {world} GPUs, gradients summed on the device, then 1 RCCL "
                                       f"gradient exchange per step (multiview.GradExchange, format {exchange.mode}: "
@@ -1024,6 +1050,38 @@ def main():
 def dropin_ring_stats():
     from dreamscene_amd import dropin
     return {"enabled": dropin.ENABLED, "rings": dropin.stats()}
+
+
+GRAD_LEAVES = ("means3D", "shs", "opacities", "scales", "rotations")
+DUMP_BYTES = 64 << 20
+
+
+def last_step_outputs(outs, m2d_grads, leaf_grads, arena) -> dict:
+    """What a caller of the timed path received from one step, as host arrays: every view's image, radii, depth_alpha and
+    means2D gradient stacked over the views, and the parameter gradients -- per view where autograd returned them
+    (`leaf_grads`: one tuple per view in GRAD_LEAVES order), else the arena's sum over the step's views."""
+    stack = lambda ts: torch.stack([t_.detach() for t_ in ts]).cpu().numpy()
+    res = {"image": stack([o[0] for o in outs]), "radii": stack([o[1] for o in outs]),
+           "depth_alpha": stack([o[2] for o in outs]), "means2D_grad": stack(list(m2d_grads))}
+    for i, n in enumerate(GRAD_LEAVES):
+        res[f"{n}_grad"] = (stack([g[i] for g in leaf_grads]) if leaf_grads is not None else
+                            arena.views[n].detach().cpu().numpy())
+    return res
+
+
+def write_outputs(out_dir, arrays, budget=DUMP_BYTES, seed=0) -> None:
+    """out_dir/<name>.npy per array: float64 stays float64, anything else becomes float32. Every array gets an equal share
+    of `budget` bytes (headers included); a larger one is replaced by a sample of its flattened entries, the same sorted
+    indices in every run (numpy default_rng(seed)), so that two builds' files compare entry for entry."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = budget // max(1, len(arrays)) - 256              # (room for the .npy header)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        cap = share // a.itemsize
+        if a.size > cap:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(seed).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def measure_allreduce(arena, dev, backend, allreduce_scalars, reps: int = 20):

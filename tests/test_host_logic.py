@@ -67,7 +67,7 @@ def test_view_stats_single_process():
 
 
 def test_bench_self_launch_command():
-    """`python bench.py --gpus N` without a launcher environment re-execs itself under torch.distributed.run with one rank
+    """`python bench.py --gpus N` without a launcher environment starts itself under torch.distributed.run with one rank
     per GPU on 127.0.0.1 (the flag used to be parsed and ignored)."""
     import importlib.util
     import os

@@ -153,13 +153,13 @@ def test_bench_two_ranks_one_gpu(built_lib, tmp_path):
 
 def test_bench_gpus_flag_launches_the_ranks_itself(built_lib):
     """`python bench.py --gpus 2` with NO launcher around it (the flag was parsed and ignored, the run
-    measured one GPU): the script re-execs under torch.distributed.run, two ranks come up, rank 0 prints one line with
+    measured one GPU): the script starts itself under torch.distributed.run, two ranks come up, rank 0 prints one line with
     n_gpus = 2, the all-reduce of the real arena is timed (`rccl`) and the exchange format is measured, then chosen."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(GSR_BENCH_BACKEND="gloo", GSR_BENCH_SHARE_GPU="1")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--gaussians",
-           "20000", "--res", "256", "--no-cpu-baseline", "--capture", "off", "--sustain-seconds", "0", "--rotate-seconds", "0",
-           "--train-seconds", "0", "--exchange-probe-steps", "3"]
+           "20000", "--res", "256", "--full", "--no-cpu-baseline", "--capture", "off", "--sustain-seconds", "0",
+           "--rotate-seconds", "0", "--train-seconds", "0", "--exchange-probe-steps", "3"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]

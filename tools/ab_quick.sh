@@ -5,7 +5,7 @@ for cfg in "" "--gaussians 2000000 --res 512"; do
   echo "== $cfg"
   for r in 1 2; do for v in new old; do
     if [ $v = old ]; then export GSR_LIB=$ROOT/dreamscene_amd/libgsrast_prev.so; else unset GSR_LIB; fi
-    timeout 300 python bench.py --no-cpu-baseline --no-dropin --sustain-seconds 0 --rotate-seconds 0 $cfg </dev/null > $O/b.json 2>$O/b.err
+    timeout 300 python bench.py --full --no-cpu-baseline --no-dropin --sustain-seconds 0 --rotate-seconds 0 $cfg </dev/null > $O/b.json 2>$O/b.err
     python -c "import json; d=json.load(open('$O/b.json')); print('$v $r', d['value'], d['roofline']['stage_us_per_view'])"
   done; done
 done

@@ -7,7 +7,7 @@ O=$ROOT/gpurun_out/$TAG; mkdir -p $O
 cd $ROOT
 timeout 1200 python -m pytest tests -m gpu -q --maxfail=12 "$@" </dev/null > $O/pytest.log 2>&1; echo "pytest rc=$?"; grep -E "^(FAILED|ERROR)|passed|failed" $O/pytest.log | tail -20
 timeout 120 python -c "import __graft_entry__ as g; g.smoke()" </dev/null > $O/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $O/smoke.log
-timeout 300 python bench.py </dev/null --no-cpu-baseline > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+timeout 300 python bench.py </dev/null --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
 python - <<PY
 import json
 try:
@@ -17,5 +17,5 @@ except Exception as e:
     print("no bench line:", e)
 PY
 cd /tmp && export TMPDIR=/tmp
-timeout 300 rocprofv3 --kernel-trace --stats -d $O/trace -o trace -- python $ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-dropin --sustain-seconds 0 --rotate-seconds 0 --train-seconds 0 > $O/trace.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats -d $O/trace -o trace -- python $ROOT/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-dropin --sustain-seconds 0 --rotate-seconds 0 --train-seconds 0 > $O/trace.log 2>&1
 python $ROOT/tools/kstats.py $O/trace > $O/kernel_stats.txt 2>&1; rm -rf $O/trace; head -40 $O/kernel_stats.txt

@@ -10,4 +10,4 @@ cp gpurun_out/r03_dropin/bench_line.json $GSR_PROFILE_OUT/r03_dropin_bench_line.
 rm -rf gpurun_out/r03_dropin/trace gpurun_out/r03_dropin/pmc_*
 head -12 $GSR_PROFILE_OUT/r03_dropin_kernel_stats.txt | cut -c1-140
 bash tools/sweep.sh r03
-timeout 600 python bench.py > gpurun_out/r03_bench_default.json 2> gpurun_out/r03_bench_default.err; tail -c 1500 gpurun_out/r03_bench_default.json
+timeout 600 python bench.py --full > $GSR_PROFILE_OUT/r03_bench_default.json 2> $GSR_PROFILE_OUT/r03_bench_default.err; tail -c 1500 $GSR_PROFILE_OUT/r03_bench_default.json
