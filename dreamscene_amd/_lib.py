@@ -98,6 +98,16 @@ class GsrRowSet(C.Structure):
     _fields_ = [("rows", C.c_int32), ("n_regions", C.c_int32), ("regions", GsrRowRegion * GSR_ROWSET_MAX_REGIONS)]
 
 
+GSR_MAX_DISP_VIEWS = 16
+GSR_DISP_STATS_FLOATS = 4
+
+
+class GsrDispViews(C.Structure):
+    _fields_ = [("n_views", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("reserved_", C.c_int32),
+                ("depth_alpha", _f * GSR_MAX_DISP_VIEWS), ("dL_ddepth_alpha", _f * GSR_MAX_DISP_VIEWS),
+                ("focal", C.c_float * GSR_MAX_DISP_VIEWS)]
+
+
 # every symbol include/gsrast.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("gsr_adam_step", C.c_int, [C.POINTER(GsrAdamGroup), C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,
@@ -146,6 +156,15 @@ SYMBOLS = [
                                           C.c_void_p, C.c_void_p]),
     ("gsr_knn_scratch_bytes", C.c_size_t, [C.c_int32]),
     ("gsr_knn_mean_dist2", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("gsr_disp_scratch_bytes", C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    ("gsr_disp_forward", C.c_int, [C.POINTER(GsrDispViews), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                   C.c_void_p]),
+    ("gsr_disp_backward", C.c_int, [C.POINTER(GsrDispViews), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                    C.c_void_p]),
+    ("gsr_tv_scratch_bytes", C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    ("gsr_tv_forward", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
+                                 C.c_void_p]),
+    ("gsr_tv_backward", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("gsr_backward", C.c_int, [C.POINTER(GsrView), C.POINTER(GsrGaussians), C.POINTER(GsrGeom), C.POINTER(GsrBinning),
                                C.POINTER(GsrImages), C.POINTER(GsrImageGrads), C.POINTER(GsrGrads), C.c_void_p,
                                C.c_void_p]),

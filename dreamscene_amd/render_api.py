@@ -62,11 +62,13 @@ def _cam_tensors(cam, device, dtype=torch.float32):
 def object_render(params: GaussianParams, camera, bg_color: torch.Tensor, scaling_modifier: float = 1.0,
                   score_flag: bool = False, rasterizer_cls=None, settings_cls=None, test: bool = True,
                   black_video: bool = False, sh_deg_aug_ratio: float = 0.1, bg_aug_ratio: float = 0.3,
-                  shs_aug_ratio: float = 1.0, scale_aug_ratio: float = 1.0, rng=random, host_noise: bool = False):
+                  shs_aug_ratio: float = 1.0, scale_aug_ratio: float = 1.0, rng=random, host_noise: bool = False,
+                  fused_disp: bool = False):
     """SceneGaussian.object_render / score_render. test=True (the default here): no random augmentation. test=False:
     the reference's training-time augmentations, drawing from `rng` (Python's `random`) and torch's generator in the
     reference's order. host_noise: draw the torch noise on the CPU generator and move it to the parameters' device (so
-    that a seeded run reproduces the CPU-captured fixture on a GPU)."""
+    that a seeded run reproduces the CPU-captured fixture on a GPU). fused_disp: the disp post-processing through
+    glue.disp_from_depth_alpha (the same forward bits, no host read; off by default)."""
     if rasterizer_cls is None or settings_cls is None:
         from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer
         rasterizer_cls = rasterizer_cls or GaussianRasterizer
@@ -107,14 +109,18 @@ def object_render(params: GaussianParams, camera, bg_color: torch.Tensor, scalin
         score, rendered_image, radii, depth_alpha = res
     else:
         rendered_image, radii, depth_alpha = res
-    depth, alpha = torch.chunk(depth_alpha, 2)
-    focal = 1 / (2 * math.tan(camera.FoVx / 2))
-    disp = focal / (depth + (alpha * 10) + 1e-5)
-    try:
-        min_d = disp[alpha <= 0.1].min()
-    except Exception:
-        min_d = disp.min()
-    disp = torch.clamp((disp - min_d) / (disp.max() - min_d), 0.0, 1.0)
+    if fused_disp:
+        from .glue import disp_from_depth_alpha
+        disp, alpha = disp_from_depth_alpha(depth_alpha, camera.FoVx)
+    else:
+        depth, alpha = torch.chunk(depth_alpha, 2)
+        focal = 1 / (2 * math.tan(camera.FoVx / 2))
+        disp = focal / (depth + (alpha * 10) + 1e-5)
+        try:
+            min_d = disp[alpha <= 0.1].min()
+        except Exception:
+            min_d = disp.min()
+        disp = torch.clamp((disp - min_d) / (disp.max() - min_d), 0.0, 1.0)
     out = {"image": rendered_image, "depth": disp, "alpha": alpha, "viewspace_points": screenspace_points,
            "visibility_filter": radii > 0, "radii": radii, "scales": scales}
     if score_flag:

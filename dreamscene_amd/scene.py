@@ -157,10 +157,11 @@ def rasterize_models_views(settings_list, models: Sequence, means2D: torch.Tenso
 def scene_render(models: Sequence, camera, bg_color: torch.Tensor, active_sh_degree: int,
                  scaling_modifier: float = 1.0, black_video: bool = False, sh_deg_aug_ratio: float = 0.1,
                  bg_aug_ratio: float = 0.3, shs_aug_ratio: float = 1.0, scale_aug_ratio: float = 1.0,
-                 test: bool = False, no_grad: bool = False, rng: random.Random = random):
+                 test: bool = False, no_grad: bool = False, rng: random.Random = random, fused_disp: bool = False):
     """SceneGaussian.scene_render (scene_gaussian.py:673-893) over the fused path: same random augmentation decisions
     in the same order, same output dict. The noise samples are drawn with torch.randn in the concatenated index space
-    (the reference draws them with randn_like on the concatenated tensors)."""
+    (the reference draws them with randn_like on the concatenated tensors). fused_disp: the disp post-processing through
+    glue.disp_from_depth_alpha (the same forward bits, no host read; off by default)."""
     from .rasterizer import GaussianRasterizationSettings
     first = _leaves(models[0])[0]
     dev = first.device
@@ -188,13 +189,17 @@ def scene_render(models: Sequence, camera, bg_color: torch.Tensor, active_sh_deg
     scale_noise = torch.randn((P, 3), dtype=torch.float32, device=dev) if (rng.random() < scale_aug_ratio and not test) else None
     rendered_image, radii, depth_alpha, scales = rasterize_models(settings, models, screenspace_points, scale_noise,
                                                                   sh_noise)
-    depth, alpha = torch.chunk(depth_alpha, 2)
-    focal = 1 / (2 * math.tan(camera.FoVx / 2))
-    disp = focal / (depth + (alpha * 10) + 1e-5)
-    try:
-        min_d = disp[alpha <= 0.1].min()
-    except Exception:
-        min_d = disp.min()
-    disp = torch.clamp((disp - min_d) / (disp.max() - min_d), 0.0, 1.0)
+    if fused_disp:
+        from .glue import disp_from_depth_alpha
+        disp, alpha = disp_from_depth_alpha(depth_alpha, camera.FoVx)
+    else:
+        depth, alpha = torch.chunk(depth_alpha, 2)
+        focal = 1 / (2 * math.tan(camera.FoVx / 2))
+        disp = focal / (depth + (alpha * 10) + 1e-5)
+        try:
+            min_d = disp[alpha <= 0.1].min()
+        except Exception:
+            min_d = disp.min()
+        disp = torch.clamp((disp - min_d) / (disp.max() - min_d), 0.0, 1.0)
     return {"image": rendered_image, "depth": disp, "alpha": alpha, "viewspace_points": screenspace_points,
             "visibility_filter": radii > 0, "radii": radii, "scales": scales}

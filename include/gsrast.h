@@ -459,6 +459,42 @@ int gsr_rowmsg_apply(const GsrRowSet* set, const void* msgs, uint64_t msg_stride
 int gsr_rowmsg_apply_slices(const GsrRowSet* set, const void* msgs, uint64_t msg_stride, int32_t n_slices, int32_t slice_rows,
                             uint32_t cap, uint64_t* status, uint64_t* touched, void* stream);
 
+/* ---- per-pixel glue between the rasterizer and the loss (dreamscene_amd/glue.py; SEMANTICS.md "disp post-processing and
+ * tv_loss") --------------------------------------------------------------------------------------------------------------------
+ * disp post-processing, scene_gaussian.py:651-658, :874-881, :1023-1032, for up to GSR_MAX_DISP_VIEWS views of one size per call:
+ *   d = (1 / ((depth + alpha * 10) + 1e-5)) * focal;  m = min of d over alpha <= 0.1 (fp32 compare), or over every pixel when no
+ *   pixel qualifies;  M = max of d;  disp = clamp((d - m) / (M - m), 0, 1)  (a flat view gives NaN, as torch does).
+ * gsr_disp_forward   two launches: disp [V,1,H,W], alpha [V,1,H,W] (a copy of the alpha planes), stats [V][4] floats
+ *                    (m, M, masked flag, M - m; 16-byte aligned) which the backward reads. No host read.
+ * gsr_disp_backward  two launches: dL/d depth_alpha per view (dL_ddepth_alpha[k], [2,H,W]) from dL_ddisp [V,1,H,W] and
+ *                    dL_dalpha ([V,1,H,W] or NULL); d is recomputed. The gradients of m and M are shared evenly among the pixels
+ *                    that equal them (torch's min() / max()); their sums are formed in double in a fixed order.
+ * scratch: gsr_disp_scratch_bytes(V, H, W) bytes, 16-byte aligned, for either call (0: the shape is not accepted).
+ * tv_loss, utils/system_utils.py:39-47, x [B,C,H,W] fp32 contiguous, H >= 2 and W >= 2:
+ * gsr_tv_forward     two launches: *out (device fp32) = 2 (h_tv / (C (H-1) W) + w_tv / (C H (W-1))) / B, the squared differences
+ *                    in fp32 and their sums in double (fixed order). scratch: gsr_tv_scratch_bytes(B, C, H, W) bytes, 16-aligned.
+ * gsr_tv_backward    one launch: dL_dx [B,C,H,W] (stored) from the scalar *dL_dout in device memory.
+ * All of them: enqueued on `stream`, no allocation, no host synchronisation (capturable into a hipGraph). */
+#define GSR_MAX_DISP_VIEWS 16
+#define GSR_DISP_STATS_FLOATS 4
+typedef struct GsrDispViews {
+  int32_t n_views;                                   /* 1..GSR_MAX_DISP_VIEWS                                 */
+  int32_t height, width;
+  int32_t reserved_;
+  const float* depth_alpha[GSR_MAX_DISP_VIEWS];      /* view k: [2,H,W], the depth plane then the alpha plane  */
+  float* dL_ddepth_alpha[GSR_MAX_DISP_VIEWS];        /* view k: [2,H,W], written by the backward (unused by the forward) */
+  float focal[GSR_MAX_DISP_VIEWS];                   /* 1 / (2 tan(FoVx / 2)) rounded to fp32                  */
+} GsrDispViews;
+size_t gsr_disp_scratch_bytes(int32_t n_views, int32_t height, int32_t width);
+int gsr_disp_forward(const GsrDispViews* views, float* disp, float* alpha, float* stats, void* scratch, size_t scratch_bytes,
+                     void* stream);
+int gsr_disp_backward(const GsrDispViews* views, const float* stats, const float* dL_ddisp, const float* dL_dalpha, void* scratch,
+                      size_t scratch_bytes, void* stream);
+size_t gsr_tv_scratch_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
+int gsr_tv_forward(const float* x, int32_t B, int32_t C, int32_t H, int32_t W, float* out, void* scratch, size_t scratch_bytes,
+                   void* stream);
+int gsr_tv_backward(const float* x, int32_t B, int32_t C, int32_t H, int32_t W, const float* dL_dout, float* dL_dx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
