@@ -80,6 +80,23 @@ class GradArena:
         bits = ((self.reached.unsqueeze(1) >> sh) & 1).reshape(-1)[:self.P]
         return torch.nonzero(bits).reshape(-1)
 
+    def rebuild_reached(self) -> None:
+        """The reached-row bitmap from the arena's CONTENTS, for an arena something other than the HIP backward wrote (touch()):
+        a row's bit is set when any entry of the row, in any region, is non-zero -- a superset of the rows an exchange has to move.
+        One pass of torch ops over the arena, no host read. The bitmap describes nothing else afterwards (_mask_owner), and the
+        rows outside it are not promised to stay zero for K8 (zero_outside_reached is left as it is)."""
+        P = self.P
+        nz = None
+        for t in self.views.values():
+            m = (t.reshape(P, -1) != 0).any(1)
+            nz = m if nz is None else nz | m
+        bits = torch.zeros(self.reached.numel() * 64, dtype=torch.int64, device=self.reached.device)
+        bits[:P] = nz
+        sh = torch.arange(64, device=self.reached.device, dtype=torch.int64)
+        self.reached.copy_((bits.view(-1, 64) << sh).sum(1))     # (distinct bits: the sum is the OR; bit 63 wraps correctly)
+        self.reached_valid = True
+        self._mask_owner = None
+
     def nbytes(self) -> int:
         return self.flat.numel() * self.flat.element_size()
 
@@ -327,9 +344,8 @@ class GradExchange:
         can differ from zero, not 11 + 3 K  (14 of 59 at D = 0, 23 at D = 1, 38 at D = 2);
       * rows of Gaussians no pixel composited are identically zero: culled ones (indoor scenes: 94 % of 2 M per view) and
         everything behind the opaque front layers of an object (early termination T < 1e-4).
-    Wire formats (`mode`; "auto" picks per step: on a cuda arena with K8's reached bitmap between the message form of `sparse_rs` and
-    `dense` from the capacities the message form has learnt -- no host read --, elsewhere from the non-zero row fraction, one small
-    host read):
+    Wire formats (`mode`; "auto" picks per step: on a cuda arena between the message form of `sparse_rs` and `dense` from the
+    capacities the message form has learnt -- no host read --, on a CPU arena from the non-zero row fraction, one small host read):
       * "dense": all-reduce of [geometry 11 P | active SH columns 3 (D+1)^2 P] -- the arena itself when D is the stored
         degree (zero-copy), else a packed staging buffer (one strided copy each way);
       * "direct": the dense exchange spelled as the two one-hop steps a fully connected xGMI node allows: ONE all-to-all
@@ -351,7 +367,7 @@ class GradExchange:
         the dense ring's 206 MB. Three small host reads per step (row counts).
     `reduce_scatter_adam` is the sharded-optimizer form of the dense exchange (flat parameter arena required).
 
-    "rows" on a cuda arena whose reached bitmap K8 left is valid takes the DEVICE form (`_RowMessages`): one pack launch, one
+    "rows" on a cuda arena takes the DEVICE form (`_RowMessages`): one pack launch, one
     fixed-size all-gather of self-describing messages, one apply launch that stores the rank-ordered sums -- no count on the
     host, no zero-fill of the arena, no index list on the wire. The capacity is speculated (it starts at P / 4 rows and follows
     1.25 x the largest count any rank ever sent); `strict` (default True) polls the apply kernel's status word -- written when
@@ -360,7 +376,15 @@ class GradExchange:
     finish()); a step that overflowed leaves its arena UN-reduced and is counted in `overflowed_steps` -- for loops whose
     consumer can tolerate or detect that (bench.py checks the counter after its timed region).
     reduce(async_op=True): the whole exchange on the exchange's own stream, ordered behind the caller's current stream;
-    ExchangeHandle.wait() joins -- the per-view statistics all-reduce and the optimizer's prologue run beside it."""
+    ExchangeHandle.wait() joins -- the per-view statistics all-reduce and the optimizer's prologue run beside it.
+
+    INVARIANT: the wire plan -- which collectives run, in which order, with which sizes -- is a function of rank-invariant state
+    only: mode, world size, row_floats, P, whether the arena is on the device, and the learnt capacities (`_rows_cap`, `_rs_caps`:
+    every rank reads them from the same message headers). Ranks that planned differently would issue different collectives: the
+    exchange would hang or corrupt the sum. What a rank's views were is NOT part of that state: a rank with no view this step, or
+    whose views came through a four-argument callback, holds no valid bitmap from K8 (GradArena.reached_valid) -- the device forms
+    then rebuild the bitmap from the arena (GradArena.rebuild_reached: one pass of torch ops, no host read) and speak the same
+    protocol as everyone else. The validity of the bitmap decides how a rank BUILDS its message, never which protocol it speaks."""
 
     GEOM = ("means3D", "scales", "rotations", "opacities")
 
@@ -435,11 +459,20 @@ class GradExchange:
         return self._dev_rows.rowset([(v["means3D"], 3, 3), (v["scales"], 3, 3), (v["rotations"], 4, 4), (v["opacities"], 1, 1),
                                       (v["shs"], 3 * nb, 3 * K)], P)
 
+    def _bitmap(self) -> torch.Tensor:
+        """The arena's reached-row bitmap, rebuilt from its contents when K8 did not leave it valid (GradArena.rebuild_reached:
+        a rank with no view this step, a four-argument callback, a torch write): the device forms run on EVERY rank of a cuda
+        arena, whatever this rank's views were."""
+        if not self.arena.reached_valid:
+            self.arena.rebuild_reached()
+        return self.arena.reached
+
     def _message(self):
-        """(idx, rows): this rank's non-zero rows as a message, indices ascending. On a cuda arena whose reached bitmap K8 left
-        is valid: ONE pack through the HIP library (idx int32); otherwise the torch path (idx int64)."""
+        """(idx, rows): this rank's non-zero rows as a message, indices ascending. On a cuda arena: ONE pack through the HIP
+        library from the reached bitmap (idx int32); on a CPU arena the torch path (idx int64)."""
         a = self.arena
-        if self._dev_rows is not None and getattr(a, "reached_valid", False):
+        if self._dev_rows is not None:
+            self._bitmap()
             guess = getattr(self, "_last_n", 0)
             idx, rows = self._dev_rows.pack(self._arena_rowset(), a.reached, self.row_floats, int(guess * 1.25))
             self._last_n = int(idx.numel())
@@ -543,13 +576,14 @@ class GradExchange:
         if self._rs_caps[0] == 0:
             self._rs_caps = [min((max(per // 4, 512) + 511) // 512 * 512, lim), min((max(per // 2, 512) + 511) // 512 * 512, lim)]
         rs = self._arena_rowset()
+        mask = self._bitmap()
         r = dist.get_rank(self.group)
         rows_here = max(0, min(per, P - r * per))
         tries = 0
         while True:
             cap1, cap2 = self._rs_caps
             send1, recv1, own2, all2 = self._msgs.slice_buffers(P, F, W, per, cap1, cap2)
-            self._msgs.pack_slices(rs, self.arena.reached, W, per, cap1)
+            self._msgs.pack_slices(rs, mask, W, per, cap1)
             _all_to_all_single(recv1, send1, self.group)
             self._msgs.reduce_owned(rows_here, per, F, W, cap1, cap2)
             _all_gather_into(all2, own2, self.group)
@@ -583,11 +617,12 @@ class GradExchange:
         if self._rows_cap == 0:
             self._rows_cap = min((max(P // 4, 1024) + 1023) // 1024 * 1024, (P + 1023) // 1024 * 1024)
         rs = self._arena_rowset()
+        mask = self._bitmap()
         tries = 0
         while True:
             cap = self._rows_cap
             msg, allm, nbytes = self._msgs.buffers(P, F, W, cap)
-            self._msgs.pack(rs, self.arena.reached, cap)
+            self._msgs.pack(rs, mask, cap)
             _all_gather_into(allm, msg, self.group)
             self._msgs.apply(rs, W, cap, touched=self.arena.reached)       # (the union bitmap: _kept_sparse)
             self._settle = "rows"
@@ -613,7 +648,9 @@ class GradExchange:
         mode = self.mode
         idx = counts = None
         msg_rows = None
-        on_device = self._dev_rows is not None and getattr(self.arena, "reached_valid", False)
+        # (the plan depends on rank-invariant state only -- class docstring, INVARIANT: NOT on whether K8 left this rank's bitmap
+        #  valid; the device forms rebuild it where it is not, _bitmap)
+        on_device = self._dev_rows is not None
         if mode == "auto" and on_device:
             # no count on the host: the sparse reduce-scatter in its message form unless the capacities it has learnt say that it
             # would move more than half of what the dense ring moves (the same decision on every rank: the capacities are)
@@ -631,7 +668,7 @@ class GradExchange:
         if mode == "rows" and on_device:
             self._reduce_rows_device(W)
             return
-        if mode in ("auto", "rows"):      # ("sparse_rs" counts per owner itself)
+        if mode in ("auto", "rows"):      # (CPU arenas: the host-count forms; "sparse_rs" counts per owner itself)
             idx, msg_rows = self._message()
             cnt = torch.empty(W, dtype=torch.int64, device=idx.device)
             _all_gather_into(cnt, torch.tensor([idx.numel()], dtype=torch.int64, device=idx.device), self.group)
@@ -671,7 +708,7 @@ class GradExchange:
             self.last = dict(format="direct", row_floats=F, bytes_per_rank=int(2 * (W - 1) / W * 4 * n))
             return
         if mode == "sparse_rs":
-            if self._dev_rows is not None and getattr(self.arena, "reached_valid", False):
+            if on_device:
                 self._reduce_sparse_rs_device(W)
             else:
                 self._reduce_sparse_rs(W)

@@ -333,3 +333,29 @@ def test_arena_knows_when_its_rows_outside_the_bitmap_are_zero():
     assert not b.verify_zero_outside() and b.verify_zero_outside(("means3D", "shs"))
     b.reached[0] = 1 << 7
     assert b.verify_zero_outside()
+
+
+def test_arena_rebuilds_its_bitmap_from_its_contents():
+    """GradArena.rebuild_reached (what a rank without a valid K8 bitmap -- no view this step, a four-argument callback -- packs its
+    device-form message from): bit i is set exactly when row i has a non-zero entry in ANY region, SH columns above an active
+    degree included; the partial last word and bit 63 of a word (the sign bit of the int64) come out right."""
+    import torch
+    from dreamscene_amd import multiview
+    P, K = 130, 16
+    a = multiview.GradArena(P, K, "cpu")
+    a.views["means3D"][0, 2] = 1.0
+    a.views["scales"][63, 0] = -2.0
+    a.views["rotations"][64, 3] = 3.0
+    a.views["opacities"][100, 0] = 4.0
+    a.views["shs"][127, 15, 2] = 5.0                # (a column above degree 0: still a non-zero row of the arena)
+    a.views["shs"][129, 0, 0] = -0.0                # (negative zero is zero)
+    a.views["shs"][128, 1, 1] = 1e-30
+    a._mask_owner = object()
+    a.touch()
+    a.rebuild_reached()
+    assert a.reached_valid and a._mask_owner is None and not a.zero_outside_ok()
+    assert a.reached_rows().tolist() == [0, 63, 64, 100, 127, 128]
+    assert a.verify_zero_outside(regions=[n for n, _ in multiview.FIELDS])
+    a.flat.zero_()
+    a.rebuild_reached()
+    assert a.reached_rows().numel() == 0 and int(a.reached.abs().sum()) == 0

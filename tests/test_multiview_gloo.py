@@ -3,8 +3,10 @@ share of the views forward+backward and the per-view parameter gradients are sum
 the packed arena; the result must equal the sequential accumulation over all views that the reference performs
 (training/object_trainer.py:302-382). The renderer is the CPU oracle here (test infrastructure): the HIP rasterizer
 cannot run without a GPU, and the data-parallel logic is renderer-agnostic."""
+import json
 import os
 import socket
+from datetime import timedelta
 
 import numpy as np
 import pytest
@@ -63,9 +65,11 @@ def _worker(rank, world, port, n_views, out_dir):
     params = {k: torch.tensor(v) for k, v in g.items()}
     arena = multiview.GradArena(200, 16, "cpu")
     outs = multiview.render_views_data_parallel(_oracle_view_fn(), params, cams, ups, arena)
-    # per-view densification statistics, reduced so every replica decides identically
+    # per-view densification statistics, reduced so every replica decides identically: one collective per view SLOT on every
+    # rank (a rank with fewer views -- or none -- contributes a view that reached nothing: zero norm, invisible, radius 0)
     acc = None
-    for o in outs:
+    for j in range(-(-n_views // world)):
+        o = outs[j] if j < len(outs) else dict(means2D_grad=torch.zeros(200, 3), radii=torch.zeros(200, dtype=torch.int32))
         st = multiview.reduce_view_stats(o["means2D_grad"], o["radii"])
         acc = st if acc is None else (acc[0] + st[0], acc[1] + st[1], torch.maximum(acc[2], st[2]))
     np.savez(os.path.join(out_dir, f"rank{rank}.npz"), flat=arena.flat.numpy(), norm=acc[0].numpy(), vis=acc[1].numpy(),
@@ -74,7 +78,7 @@ def _worker(rank, world, port, n_views, out_dir):
     dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("n_views", [2, 4])
+@pytest.mark.parametrize("n_views", [1, 2, 3, 4])
 def test_two_rank_allreduce_equals_sequential_accumulation(tmp_path, n_views):
     world = 2
     port = _free_port()
@@ -103,6 +107,80 @@ def test_two_rank_allreduce_equals_sequential_accumulation(tmp_path, n_views):
     np.testing.assert_allclose(r0["norm"], norm.numpy(), atol=1e-6)
     assert np.array_equal(r0["vis"], vis.numpy()) and np.array_equal(r0["maxr"], maxr.numpy())
     assert np.array_equal(r0["norm"], r1["norm"])
+
+
+# ------------------------------------------------------------------------------------------------ empty and uneven shards
+SHARD_STEPS = (1, 2, 4)      # views per step on 3 ranks: two ranks empty, one rank empty, an uneven 2 + 1 + 1 split
+STYLES = ("keyword", "positional", "four")
+
+
+def _styled(fn, style):
+    """The oracle callback in each of the three contracts render_views_data_parallel accepts."""
+    if style == "keyword":
+        return fn
+    if style == "positional":
+        return lambda params, cam, grad_out, upstream, acc: fn(params, cam, grad_out, upstream, acc)
+    return lambda params, cam, grad_out, upstream: fn(params, cam, grad_out, upstream, False)
+
+
+def _shards_worker(rank, world, port, mode, out_dir):
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=timedelta(seconds=60))
+    torch.set_num_threads(2)
+    from dreamscene_amd import multiview
+    g, cams, ups = _scene(max(SHARD_STEPS))
+    params = {k: torch.tensor(v) for k, v in g.items()}
+    arena = multiview.GradArena(200, 16, "cpu")
+    ex = multiview.GradExchange(arena, sh_degree=3, mode=mode)
+    fn = _oracle_view_fn()
+    flats, fmts = [], []
+    for s, n in enumerate(SHARD_STEPS):        # one arena, one exchange: consecutive steps, as a trainer runs them
+        multiview.render_views_data_parallel(_styled(fn, STYLES[s % 3]), params, cams[:n], ups[:n], arena, exchange=ex)
+        flats.append(arena.flat.numpy().copy())
+        fmts.append(ex.last["format"])
+    np.savez(os.path.join(out_dir, f"rank{rank}.npz"), flats=np.stack(flats), fmts=json.dumps(fmts))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("mode", ["dense", "rows", "direct", "sparse_rs", "auto"])
+def test_three_ranks_with_empty_and_uneven_shards(tmp_path, mode):
+    """render_views_data_parallel + GradExchange on 3 ranks when some ranks have no view and the others hold 1 or 2: every
+    format leaves, on every rank, the float64 sum of the per-view oracle gradients (each region within 1e-6 of its own largest
+    entry), replicas bit-identical, rows no view reached exactly zero. P = 200 is no multiple of 3: the owner slices of
+    `direct` / `sparse_rs` are uneven."""
+    from dreamscene_amd import multiview
+    world = 3
+    mp.spawn(_shards_worker, args=(world, _free_port(), mode, str(tmp_path)), nprocs=world, join=True)
+    rs = [np.load(tmp_path / f"rank{r}.npz") for r in range(world)]
+    fmts = json.loads(str(rs[0]["fmts"]))
+    assert all(json.loads(str(r["fmts"])) == fmts for r in rs), "the ranks chose different wire formats"
+    assert all(f in (("rows", "dense") if mode == "auto" else (mode,)) for f in fmts), fmts
+    g, cams, ups = _scene(max(SHARD_STEPS))
+    params = {k: torch.tensor(v) for k, v in g.items()}
+    fn = _oracle_view_fn()
+    per_view = []
+    for cam, up in zip(cams, ups):
+        a = multiview.GradArena(200, 16, "cpu", dtype=torch.float64)
+        fn(params, cam, a.views, up, False)
+        per_view.append(a)
+    layout = multiview.GradArena(200, 16, "cpu")
+    for s, n in enumerate(SHARD_STEPS):
+        for r in rs[1:]:
+            assert np.array_equal(rs[0]["flats"][s], r["flats"][s]), f"step {s} (n={n}): the replicas differ"
+        layout.flat.copy_(torch.from_numpy(rs[0]["flats"][s]))
+        zero = np.ones(200, dtype=bool)
+        for k in layout.views:
+            ref = np.zeros(tuple(layout.views[k].shape))
+            for a in per_view[:n]:                   # view order, float64
+                ref += a.views[k].numpy()
+            got = layout.views[k].numpy()
+            assert np.abs(ref).max() > 0
+            np.testing.assert_allclose(got, ref, rtol=0, atol=1e-6 * rel_scale(ref), err_msg=f"step {s} (n={n}): {k}")
+            zero &= ~ref.reshape(200, -1).any(1)
+        for k in layout.views:
+            assert not layout.views[k].numpy().reshape(200, -1)[zero].any(), f"step {s}: {k}: rows no view reached"
 
 
 # ------------------------------------------------------------------------------------------------ GradExchange
