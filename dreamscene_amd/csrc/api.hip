@@ -5,12 +5,11 @@ thread_local int gsr_tls_hip_error = 0;
 
 // stage launchers (preprocess.hip, binning.hip, render.hip)
 int gsr_launch_preprocess(const GsrView&, const GsrGaussians&, GsrGeom&, hipStream_t);
-int gsr_launch_preprocess_bwd(const GsrView&, const GsrGaussians&, const GsrGeom&, const GsrGrads&, hipStream_t);
 bool gsr_preprocess_views_supported(const GsrView&, const GsrGaussians&);
 int gsr_launch_preprocess_views(int n_views, const GsrView* views, const GsrGaussians* gs, GsrGeom* geoms, hipStream_t);
 bool gsr_preprocess_bwd_views_supported(const GsrView&, const GsrGaussians&, const GsrGrads&);
-int gsr_launch_preprocess_bwd_views(int n_views, const GsrView* views, const GsrGaussians* gs, const GsrGeom* geoms,
-                                    const GsrGrads* outs, hipStream_t);
+int gsr_launch_preprocess_bwd(int n_views, const GsrView* views, const GsrGaussians* gs, const GsrGeom* geoms,
+                              const GsrGrads* outs, hipStream_t, bool* restored);
 int gsr_launch_depth_order(GsrGeom&, const GsrView&, hipStream_t, GsrProfile*, int batch, size_t bstride,
                            uint64_t* n_pairs_all, bool early);
 uint64_t* gsr_pair_counts(const GsrGeom&, int32_t P);
@@ -26,7 +25,6 @@ int gsr_launch_render_bwd_views(int n, const GsrView* views, const GsrGeom* geom
                                 const GsrImages* imgs, const GsrImageGrads* igs, GsrGrads* outs, hipStream_t, GsrProfile*);
 int gsr_launch_work_order_fwd(int n, const GsrView* views, const GsrBinning* bs, const GsrImages* imgs, hipStream_t);
 int gsr_launch_work_order_bwd(int n, const GsrView* views, const GsrBinning* bs, const GsrImages* imgs, hipStream_t);
-bool gsr_k8_form_restores(bool views_entry, const GsrView& v, const GsrGaussians& g, const GsrGrads& out);
 int gsr_launch_render_bwd(const GsrView&, const GsrGeom&, const GsrBinning&, const GsrImages&, const GsrImageGrads&,
                           GsrGrads&, hipStream_t, GsrProfile*);
 
@@ -438,12 +436,13 @@ int gsr_backward(const GsrView* v, const GsrGaussians* g, const GsrGeom* geom, c
   if (rc) return rc;
   rc = backward_render(v, geom, b, img, ig, out, stream, prof);
   if (rc) return rc;
+  bool restored;
   {
     GsrStageTimer t(prof, stream, GSR_STAGE_PREPROCESS_BWD);
-    rc = gsr_launch_preprocess_bwd(*v, *g, *geom, *out, stream);
+    rc = gsr_launch_preprocess_bwd(1, v, g, geom, out, stream, &restored);
     if (rc) return rc;
   }
-  if (out->scratch_clean && !gsr_k8_form_restores(false, *v, *g, *out)) return clear_scratch(v, out, stream);
+  if (out->scratch_clean && !restored) return clear_scratch(v, out, stream);
   return GSR_OK;
 }
 
@@ -516,21 +515,23 @@ int gsr_backward_views(int32_t n_views, const GsrView* views, const GsrGaussians
       o.dL_dcov3D = o0.dL_dcov3D;      // (o.scene stays view k's own table: same model tensors, its own dL_dscales_out)
       o.accumulate = (k > 0) ? 1 : o0.accumulate;
       GsrStageTimer t(prof, stream, GSR_STAGE_PREPROCESS_BWD);
-      const int rc2 = gsr_launch_preprocess_bwd(views[k], gs[k], geoms[k], o, stream);
+      bool restored;
+      const int rc2 = gsr_launch_preprocess_bwd(1, &views[k], &gs[k], &geoms[k], &o, stream, &restored);
       if (rc2) return rc2;
-      if (clean && !gsr_k8_form_restores(false, views[k], gs[k], o)) {
+      if (clean && !restored) {
         const int rc3 = clear_scratch(&views[k], &outs[k], stream);
         if (rc3) return rc3;
       }
     }
   }
   if (fused) {
+    bool restored;
     {
       GsrStageTimer t(prof, stream, GSR_STAGE_PREPROCESS_BWD);
-      const int rc = gsr_launch_preprocess_bwd_views(n_views, views, gs, geoms, outs, stream);
+      const int rc = gsr_launch_preprocess_bwd(n_views, views, gs, geoms, outs, stream, &restored);
       if (rc) return rc;
     }
-    if (clean && !gsr_k8_form_restores(true, views[0], *g, outs[0]))
+    if (clean && !restored)
       for (int k = 0; k < n_views; ++k) {
         const int rc = clear_scratch(&views[k], &outs[k], stream);
         if (rc) return rc;

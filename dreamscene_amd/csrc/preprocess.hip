@@ -2166,46 +2166,43 @@ static uint32_t scene_tables(const GsrScene& sc, const GsrSceneGrads* sgr, Scene
   return (uint32_t)blk;
 }
 
+// One launch for the runtime SH stride K: f(std::integral_constant<int, KT>) for the KT of KTs that equals K, then the
+// launch check. Only the listed KTs are instantiated; any other K is GSR_EINVAL.
+template <int... KTs, class F>
+static int launch_sh(int K, F&& f) {
+  if (!((K == KTs && (f(std::integral_constant<int, KTs>{}), true)) || ...)) return GSR_EINVAL;
+  GSR_HIP(hipGetLastError());
+  return GSR_OK;
+}
+// the single-view kernels: compile-time strides read their rows directly (no LDS); every other stride runs the generic
+// KT = 0 kernel, which stages the rows through LDS
+static int fixed_sh(int K) { return K == 16 || K == 9 || K == 4 || K == 1 ? K : 0; }
+// a runtime flag -> std::true_type / std::false_type
+template <class F>
+static void with_flag(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
+
 int gsr_launch_preprocess(const GsrView& v, const GsrGaussians& g, GsrGeom& geom, hipStream_t stream) {
+  uint32_t ss_words = 0;
+  uint32_t* ss = gsr_depth_sort_state(geom, v.P, &ss_words);
   if (g.scene) {
     SceneTab t; SceneGradTab gt;
     const uint32_t nbs = scene_tables(*g.scene, nullptr, t, gt);
     const size_t lds = gsr_preprocess_lds_bytes(v.sh_stride);
-    uint32_t ss_words = 0;
-    uint32_t* ss = gsr_depth_sort_state(geom, v.P, &ss_words);
-#define GSR_LAUNCH_K1S(KT)                                                                                         \
-  hipLaunchKernelGGL((k_preprocess<KT, true, SceneTab>), dim3(nbs), dim3(256), (KT) > 0 ? 0 : lds, stream, v, g, t, \
-                     geom.splat, geom.radii, geom.tiles_touched, gsr_depth_keys(geom, v.P), gsr_tile_rects(geom, v.P), \
-                     ss, ss_words)
-    switch (v.sh_stride) {
-      case 16: GSR_LAUNCH_K1S(16); break;
-      case 9: GSR_LAUNCH_K1S(9); break;
-      case 4: GSR_LAUNCH_K1S(4); break;
-      case 1: GSR_LAUNCH_K1S(1); break;
-      default: GSR_LAUNCH_K1S(0); break;
-    }
-#undef GSR_LAUNCH_K1S
-    GSR_HIP(hipGetLastError());
-    return GSR_OK;
+    return launch_sh<16, 9, 4, 1, 0>(fixed_sh(v.sh_stride), [&](auto kt) {
+      hipLaunchKernelGGL((k_preprocess<kt, true, SceneTab>), dim3(nbs), dim3(256), kt > 0 ? 0 : lds, stream, v, g, t,
+                         geom.splat, geom.radii, geom.tiles_touched, gsr_depth_keys(geom, v.P), gsr_tile_rects(geom, v.P),
+                         ss, ss_words);
+    });
   }
   const uint32_t nb = gsr_num_blocks(v.P);
   const size_t lds = g.shs ? gsr_preprocess_lds_bytes(v.sh_stride) : 0;
-  // compile-time strides read their rows directly (no LDS); only the generic stride stages through LDS
-  uint32_t ss_words = 0;
-  uint32_t* ss = gsr_depth_sort_state(geom, v.P, &ss_words);
-#define GSR_LAUNCH_K1(KT)                                                                                         \
-  hipLaunchKernelGGL(k_preprocess<KT>, dim3(nb), dim3(256), (KT) > 0 ? 0 : lds, stream, v, g, NoScene{}, geom.splat, \
-                     geom.radii, geom.tiles_touched, gsr_depth_keys(geom, v.P), gsr_tile_rects(geom, v.P), ss, ss_words)
-  switch (g.shs ? v.sh_stride : 0) {
-    case 16: GSR_LAUNCH_K1(16); break;
-    case 9: GSR_LAUNCH_K1(9); break;
-    case 4: GSR_LAUNCH_K1(4); break;
-    case 1: GSR_LAUNCH_K1(1); break;
-    default: GSR_LAUNCH_K1(0); break;
-  }
-#undef GSR_LAUNCH_K1
-  GSR_HIP(hipGetLastError());
-  return GSR_OK;
+  return launch_sh<16, 9, 4, 1, 0>(fixed_sh(g.shs ? v.sh_stride : 0), [&](auto kt) {
+    hipLaunchKernelGGL(k_preprocess<kt>, dim3(nb), dim3(256), kt > 0 ? 0 : lds, stream, v, g, NoScene{}, geom.splat,
+                       geom.radii, geom.tiles_touched, gsr_depth_keys(geom, v.P), gsr_tile_rects(geom, v.P), ss, ss_words);
+  });
 }
 
 // GSR_K8_SPARSE=0 keeps the dense kernels (one chain rule per visible Gaussian and view) for comparison runs.
@@ -2216,10 +2213,6 @@ static bool gsr_k8_sparse() {
   }();
   return on;
 }
-
-bool gsr_preprocess_bwd_views_supported(const GsrView& v, const GsrGaussians& g, const GsrGrads& out);
-int gsr_launch_preprocess_bwd_views(int n_views, const GsrView* views, const GsrGaussians* gs, const GsrGeom* geoms,
-                                    const GsrGrads* outs, hipStream_t stream);
 
 namespace {
 __global__ void __launch_bounds__(256) k_mask_all(unsigned long long* __restrict__ m, int64_t P) {
@@ -2238,58 +2231,8 @@ static void reached_mask_all(const GsrGrads& out, int32_t P, hipStream_t stream)
                      reinterpret_cast<unsigned long long*>(out.reached_mask), (int64_t)P);
 }
 
-// Does the form of K8 the launchers below pick honour GsrGrads.scratch_clean (zero the sums and marks it consumed)? The
-// views template does; the scene forms and the single-view kernel for colours / precomputed covariances / camera
-// gradients do not -- gsr_backward* then clears the scratch after them.
-bool gsr_k8_form_restores(bool views_entry, const GsrView& v, const GsrGaussians& g, const GsrGrads& out) {
-  if (!out.reach || !out.scratch_clean || g.scene) return false;
-  if (views_entry) return true;
-  return gsr_k8_sparse() && v.sh_stride >= 9 && !out.dL_dcolors && !out.dL_dcov3D && gsr_preprocess_bwd_views_supported(v, g, out);
-}
-
-int gsr_launch_preprocess_bwd(const GsrView& v, const GsrGaussians& g, const GsrGeom& geom, const GsrGrads& out,
-                              hipStream_t stream) {
-  // the trainers' case (SH rows, scales + rotations, no camera gradients): the sparse kernel with one view
-  if (!g.scene && gsr_k8_sparse() && v.sh_stride >= 9 && !out.dL_dcolors && !out.dL_dcov3D && gsr_preprocess_bwd_views_supported(v, g, out))
-    return gsr_launch_preprocess_bwd_views(1, &v, &g, &geom, &out, stream);
-  reached_mask_all(out, v.P, stream);
-  if (g.scene) {
-    SceneTab t; SceneGradTab gt;
-    const uint32_t nbs = scene_tables(*g.scene, out.scene, t, gt);
-    const size_t lds = gsr_preprocess_lds_bytes(v.sh_stride);
-#define GSR_LAUNCH_K8S(KT)                                                                                         \
-  hipLaunchKernelGGL((k_preprocess_bwd<KT, true, SceneTab, SceneGradTab>), dim3(nbs), dim3(256), lds, stream, v, g, t, \
-                     gt, geom.radii, out.partials, out)
-    switch (v.sh_stride) {
-      case 16: GSR_LAUNCH_K8S(16); break;
-      case 9: GSR_LAUNCH_K8S(9); break;
-      case 4: GSR_LAUNCH_K8S(4); break;
-      case 1: GSR_LAUNCH_K8S(1); break;
-      default: GSR_LAUNCH_K8S(0); break;
-    }
-#undef GSR_LAUNCH_K8S
-    GSR_HIP(hipGetLastError());
-    return GSR_OK;
-  }
-  const uint32_t nb = gsr_num_blocks(v.P);
-  const size_t lds = g.shs ? gsr_preprocess_lds_bytes(v.sh_stride) : 0;
-#define GSR_LAUNCH_K8(KT)                                                                                          \
-  hipLaunchKernelGGL(k_preprocess_bwd<KT>, dim3(nb), dim3(256), lds, stream, v, g, NoScene{}, NoScene{}, geom.radii, \
-                     out.partials, out)
-  switch (g.shs ? v.sh_stride : 0) {
-    case 16: GSR_LAUNCH_K8(16); break;
-    case 9: GSR_LAUNCH_K8(9); break;
-    case 4: GSR_LAUNCH_K8(4); break;
-    case 1: GSR_LAUNCH_K8(1); break;
-    default: GSR_LAUNCH_K8(0); break;
-  }
-#undef GSR_LAUNCH_K8
-  GSR_HIP(hipGetLastError());
-  return GSR_OK;
-}
-
 // K8 for n_views views of the same Gaussians in one pass. Supported: shs with K in {1, 4, 9, 16}, (scales, rotations),
-// no camera gradients, no scene table (the caller falls back to one gsr_launch_preprocess_bwd per view otherwise).
+// no camera gradients, no scene table (the caller falls back to one single-view K8 per view otherwise).
 bool gsr_preprocess_bwd_views_supported(const GsrView& v, const GsrGaussians& g, const GsrGrads& out) {
   const int K = v.sh_stride;
   if (g.scene)
@@ -2299,9 +2242,75 @@ bool gsr_preprocess_bwd_views_supported(const GsrView& v, const GsrGaussians& g,
          out.dL_dshs && out.dL_dscales && out.dL_drotations && out.dL_dmeans3D && out.dL_dopacities;
 }
 
-int gsr_launch_preprocess_bwd_views(int n_views, const GsrView* views, const GsrGaussians* gs, const GsrGeom* geoms,
-                                    const GsrGrads* outs, hipStream_t stream) {
+// ---- K8's form, chosen here and nowhere else: the launcher below follows it, and gsr_backward* clear the scratch by it.
+//   one view (gsr_backward; gsr_backward_views view by view):
+//     kSparseViews  no scene, K >= 9 and what the views kernel supports (gsr_preprocess_bwd_views_supported: SH rows,
+//                   scales + rotations, no camera gradients, colours or precomputed covariances) -- the trainers' case
+//     kSingleScene  otherwise, with a scene table: k_preprocess_bwd<KT, true, SceneTab, SceneGradTab>
+//     kSingle       anything else: k_preprocess_bwd<KT>
+//   n_views > 1 (gsr_backward_views, once gsr_preprocess_bwd_views_supported holds):
+//     kSceneViews   a scene table: k_preprocess_bwd_views_scene<KT>
+//     kSparseViews  K >= 9: k_preprocess_bwd_views<KT, PVS, true, KPER>
+//     kDenseViews   K <= 4: k_preprocess_bwd_views<KT, PVS> (rows of 12 floats or fewer: skipping them saves less than
+//                   the classification costs -- the 2 M indoor scene at K = 4 measured 36 us per view sparse, 33 dense)
+//   GSR_K8_SPARSE=0: no kSparseViews -- one view takes kSingle, n_views > 1 kDenseViews.
+// What follows from the form:
+//   restores_scratch  the two non-scene views forms honour GsrGrads.scratch_clean (they zero the sums and marks they
+//                     consume); after every other form gsr_backward* clears the scratch
+//   marks_every_row   only kSparseViews classifies the reached Gaussians into GsrGrads.reached_mask; before every other
+//                     form reached_mask_all sets every bit
+//   big               kSparseViews: 1 024 Gaussians per workgroup when that gives every CU a workgroup, 256 otherwise
+//                     (the form holds two workgroups per CU: 512 slots. 100 k Gaussians: 98 workgroups of 1 024 took
+//                     51 us against 26 for 391 of 256 in one shift; from ~260 k on the small workgroups need two shifts
+//                     and the large ones win)
+enum class K8Form { kSingle, kSingleScene, kSparseViews, kDenseViews, kSceneViews };
+struct K8Plan {
+  K8Form form;
+  bool restores_scratch, marks_every_row, big;
+};
+
+static K8Plan k8_plan(int n_views, const GsrView& v, const GsrGaussians& g, const GsrGrads& out) {
+  const bool sparse = gsr_k8_sparse() && v.sh_stride >= 9;
+  K8Form f;
+  if (n_views == 1)
+    f = !g.scene && sparse && !out.dL_dcolors && !out.dL_dcov3D && gsr_preprocess_bwd_views_supported(v, g, out)
+            ? K8Form::kSparseViews
+            : g.scene ? K8Form::kSingleScene : K8Form::kSingle;
+  else
+    f = g.scene ? K8Form::kSceneViews : sparse ? K8Form::kSparseViews : K8Form::kDenseViews;
+  const bool views = f == K8Form::kSparseViews || f == K8Form::kDenseViews;
+  return K8Plan{f, views && out.reach && out.scratch_clean, f != K8Form::kSparseViews,
+                (int64_t)v.P >= (int64_t)256 * kK8Block};
+}
+
+// K8 of n_views views (1: one view) in the form k8_plan picks. *restored: the scratch (GsrGrads.partials + .reach) of
+// every view is left zero under scratch_clean -- when false the caller clears it.
+int gsr_launch_preprocess_bwd(int n_views, const GsrView* views, const GsrGaussians* gs, const GsrGeom* geoms,
+                              const GsrGrads* outs, hipStream_t stream, bool* restored) {
+  const GsrView& v = views[0];
   const GsrGaussians& g = gs[0];
+  const K8Plan plan = k8_plan(n_views, v, g, outs[0]);
+  *restored = plan.restores_scratch;
+  if (plan.form == K8Form::kSingle || plan.form == K8Form::kSingleScene) {
+    const GsrGeom& geom = geoms[0];
+    const GsrGrads& out = outs[0];
+    if (plan.marks_every_row) reached_mask_all(out, v.P, stream);
+    if (plan.form == K8Form::kSingleScene) {
+      SceneTab t; SceneGradTab gt;
+      const uint32_t nbs = scene_tables(*g.scene, out.scene, t, gt);
+      const size_t lds = gsr_preprocess_lds_bytes(v.sh_stride);
+      return launch_sh<16, 9, 4, 1, 0>(fixed_sh(v.sh_stride), [&](auto kt) {
+        hipLaunchKernelGGL((k_preprocess_bwd<kt, true, SceneTab, SceneGradTab>), dim3(nbs), dim3(256), lds, stream, v, g,
+                           t, gt, geom.radii, out.partials, out);
+      });
+    }
+    const uint32_t nb = gsr_num_blocks(v.P);
+    const size_t lds = g.shs ? gsr_preprocess_lds_bytes(v.sh_stride) : 0;
+    return launch_sh<16, 9, 4, 1, 0>(fixed_sh(g.shs ? v.sh_stride : 0), [&](auto kt) {
+      hipLaunchKernelGGL(k_preprocess_bwd<kt>, dim3(nb), dim3(256), lds, stream, v, g, NoScene{}, NoScene{}, geom.radii,
+                         out.partials, out);
+    });
+  }
   K8Views vb = K8Views{};
   vb.nv = n_views;
   for (int k = 0; k < n_views; ++k) {
@@ -2318,7 +2327,7 @@ int gsr_launch_preprocess_bwd_views(int n_views, const GsrView* views, const Gsr
     vb.reach[k] = g.scene ? nullptr : reinterpret_cast<unsigned long long*>(outs[k].reach);
     if ((outs[k].reach != nullptr) != (outs[0].reach != nullptr)) return GSR_EINVAL;
   }
-  vb.restore = (!g.scene && outs[0].reach && outs[0].scratch_clean) ? 1 : 0;
+  vb.restore = plan.restores_scratch ? 1 : 0;
   // densification statistics: the views whose GsrGrads entry names the statistics tensors (all the same ones)
   GsrGrads out0 = outs[0];
   out0.stat_max_radii2D = nullptr; out0.stat_xyz_gradient_accum = nullptr; out0.stat_denom = nullptr;
@@ -2331,66 +2340,33 @@ int gsr_launch_preprocess_bwd_views(int n_views, const GsrView* views, const Gsr
     out0.stat_denom = outs[k].stat_denom;
     vb.stat_mask |= 1u << k;
   }
-  const GsrView& v = views[0];
   const size_t lds = gsr_preprocess_lds_bytes(v.sh_stride);
-  if (g.scene || !(gsr_k8_sparse() && v.sh_stride >= 9)) reached_mask_all(out0, v.P, stream);
-  if (g.scene) {
+  if (plan.marks_every_row) reached_mask_all(out0, v.P, stream);
+  if (plan.form == K8Form::kSceneViews) {
     SceneTab t; SceneGradTab gt;
     const uint32_t nbs = scene_tables(*g.scene, outs[0].scene, t, gt);
-#define GSR_LAUNCH_K8VS(KT) \
-  hipLaunchKernelGGL(k_preprocess_bwd_views_scene<KT>, dim3(nbs), dim3(256), lds, stream, v, t, gt, vb, out0)
-    switch (v.sh_stride) {
-      case 16: GSR_LAUNCH_K8VS(16); break;
-      case 9: GSR_LAUNCH_K8VS(9); break;
-      case 4: GSR_LAUNCH_K8VS(4); break;
-      case 1: GSR_LAUNCH_K8VS(1); break;
-      default: return GSR_EINVAL;
-    }
-#undef GSR_LAUNCH_K8VS
-    GSR_HIP(hipGetLastError());
-    return GSR_OK;
+    return launch_sh<16, 9, 4, 1>(v.sh_stride, [&](auto kt) {
+      hipLaunchKernelGGL(k_preprocess_bwd_views_scene<kt>, dim3(nbs), dim3(256), lds, stream, v, t, gt, vb, out0);
+    });
+  }
+  if (plan.form == K8Form::kSparseViews) {
+    const int64_t per_wg = plan.big ? kK8Block : 256;
+    const uint32_t nbr = (uint32_t)(((int64_t)v.P + per_wg - 1) / per_wg);
+    return launch_sh<16, 9>(v.sh_stride, [&](auto kt) {
+      with_flag(vb.per_view_scales, [&](auto pvs) {
+        with_flag(plan.big, [&](auto big) {
+          hipLaunchKernelGGL((k_preprocess_bwd_views<kt, pvs, true, big ? kK8Block / 256 : 1>), dim3(nbr), dim3(256), lds,
+                             stream, v, g, vb, out0);
+        });
+      });
+    });
   }
   const uint32_t nb = gsr_num_blocks(v.P);
-  // (rows of 12 floats or fewer, K <= 4: skipping them saves less than the classification costs -- the 2 M indoor scene
-  //  at K = 4 measured 36 us per view sparse, 33 dense -- so those keep the dense kernel)
-  if (gsr_k8_sparse() && v.sh_stride >= 9) {
-    // 1 024 Gaussians per workgroup when that gives every CU a workgroup, 256 otherwise (the form holds two workgroups per
-    // CU: 512 slots. 100 k Gaussians: 98 workgroups of 1 024 took 51 us against 26 for 391 of 256 in one shift; from
-    // ~260 k on the small workgroups need two shifts and the large ones win)
-    const bool big = (int64_t)v.P >= (int64_t)256 * kK8Block;
-    const int64_t per_wg = big ? kK8Block : 256;
-    const uint32_t nbr = (uint32_t)(((int64_t)v.P + per_wg - 1) / per_wg);
-#define GSR_LAUNCH_K8SP1(KT, PVS_)                                                                                         \
-  if (big) hipLaunchKernelGGL((k_preprocess_bwd_views<KT, PVS_, true, kK8Block / 256>), dim3(nbr), dim3(256), lds, stream, v, g, vb, out0); \
-  else hipLaunchKernelGGL((k_preprocess_bwd_views<KT, PVS_, true, 1>), dim3(nbr), dim3(256), lds, stream, v, g, vb, out0)
-#define GSR_LAUNCH_K8SP(KT)                                    \
-  if (vb.per_view_scales) { GSR_LAUNCH_K8SP1(KT, true); }      \
-  else { GSR_LAUNCH_K8SP1(KT, false); }
-    switch (v.sh_stride) {
-      case 16: GSR_LAUNCH_K8SP(16); break;
-      case 9: GSR_LAUNCH_K8SP(9); break;
-      default: return GSR_EINVAL;
-    }
-#undef GSR_LAUNCH_K8SP1
-#undef GSR_LAUNCH_K8SP
-    GSR_HIP(hipGetLastError());
-    return GSR_OK;
-  }
-#define GSR_LAUNCH_K8V(KT)                                                                                       \
-  if (vb.per_view_scales)                                                                                        \
-    hipLaunchKernelGGL((k_preprocess_bwd_views<KT, true>), dim3(nb), dim3(256), lds, stream, v, g, vb, out0);  \
-  else                                                                                                        \
-    hipLaunchKernelGGL((k_preprocess_bwd_views<KT, false>), dim3(nb), dim3(256), lds, stream, v, g, vb, out0)
-  switch (v.sh_stride) {
-    case 16: GSR_LAUNCH_K8V(16); break;
-    case 9: GSR_LAUNCH_K8V(9); break;
-    case 4: GSR_LAUNCH_K8V(4); break;
-    case 1: GSR_LAUNCH_K8V(1); break;
-    default: return GSR_EINVAL;
-  }
-#undef GSR_LAUNCH_K8V
-  GSR_HIP(hipGetLastError());
-  return GSR_OK;
+  return launch_sh<16, 9, 4, 1>(v.sh_stride, [&](auto kt) {
+    with_flag(vb.per_view_scales, [&](auto pvs) {
+      hipLaunchKernelGGL((k_preprocess_bwd_views<kt, pvs>), dim3(nb), dim3(256), lds, stream, v, g, vb, out0);
+    });
+  });
 }
 
 // K1 for n_views views of the same Gaussians in one pass (shs with K in {1,4,9,16}, scales + rotations, no scene table).
@@ -2424,28 +2400,12 @@ int gsr_launch_preprocess_views(int n_views, const GsrView* views, const GsrGaus
   if (g.scene) {
     SceneTab t; SceneGradTab gt;
     const uint32_t nbs = scene_tables(*g.scene, nullptr, t, gt);
-#define GSR_LAUNCH_K1VS(KT) hipLaunchKernelGGL(k_preprocess_views_scene<KT>, dim3(nbs), dim3(256), 0, stream, v, t, vb)
-    switch (v.sh_stride) {
-      case 16: GSR_LAUNCH_K1VS(16); break;
-      case 9: GSR_LAUNCH_K1VS(9); break;
-      case 4: GSR_LAUNCH_K1VS(4); break;
-      case 1: GSR_LAUNCH_K1VS(1); break;
-      default: return GSR_EINVAL;
-    }
-#undef GSR_LAUNCH_K1VS
-    GSR_HIP(hipGetLastError());
-    return GSR_OK;
+    return launch_sh<16, 9, 4, 1>(v.sh_stride, [&](auto kt) {
+      hipLaunchKernelGGL(k_preprocess_views_scene<kt>, dim3(nbs), dim3(256), 0, stream, v, t, vb);
+    });
   }
   const uint32_t nb = gsr_num_blocks(v.P);
-#define GSR_LAUNCH_K1V(KT) hipLaunchKernelGGL(k_preprocess_views<KT>, dim3(nb), dim3(256), 0, stream, v, g, vb)
-  switch (v.sh_stride) {
-    case 16: GSR_LAUNCH_K1V(16); break;
-    case 9: GSR_LAUNCH_K1V(9); break;
-    case 4: GSR_LAUNCH_K1V(4); break;
-    case 1: GSR_LAUNCH_K1V(1); break;
-    default: return GSR_EINVAL;
-  }
-#undef GSR_LAUNCH_K1V
-  GSR_HIP(hipGetLastError());
-  return GSR_OK;
+  return launch_sh<16, 9, 4, 1>(v.sh_stride, [&](auto kt) {
+    hipLaunchKernelGGL(k_preprocess_views<kt>, dim3(nb), dim3(256), 0, stream, v, g, vb);
+  });
 }

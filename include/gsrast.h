@@ -250,8 +250,9 @@ typedef struct GsrGrads {
                                  Gaussians, of which 15 MB are non-zero): one word per 64 Gaussians and view */
   int32_t scratch_clean;      /* 0: `partials` (and `reach`) hold anything on entry -- the library clears them first -- and
                                  anything on return. 1 (needs `reach`): the caller keeps both buffers between calls and
-                                 guarantees they are ALL ZERO on entry; the library leaves them all zero on return (K8 zeroes
-                                 the rows and marks it consumed), so no clear is launched at all. A call that returns an
+                                 guarantees they are ALL ZERO on entry; the library leaves them all zero on return, and
+                                 launches no clear before K7: K8's views forms without a scene zero the rows and marks they
+                                 consume, after its other forms the library clears the scratch. A call that returns an
                                  error leaves them undefined.                                                          */
   int32_t zero_outside;       /* What the caller KNOWS about the outputs as they are on entry (accumulate = 0 only; needs reached_mask,
                                  which must then hold the mask the previous writer of these buffers left):

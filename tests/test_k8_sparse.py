@@ -3,6 +3,8 @@ Gaussians of which K7 reached at most 128 compacts them and runs the chain rule 
 from coalesced clears. The scene below puts all three cases side by side -- workgroups nothing reached (opacity below
 1/255: visible, never blended), workgroups mostly reached (they stay dense) and mixed ones -- and the gradients are
 compared with the C oracle for single-view calls (write, then accumulate) and for one batched 4-view call."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -146,7 +148,10 @@ def test_rows_known_to_be_zero_are_not_written_again(built_lib):
         masks.append(arena.reached.clone())
         if step == 1:
             arena.views["shs"].mul_(2.0)         # a torch op on a view of the arena: the next backward must not trust the bitmap
-    assert not torch.equal(masks[0], masks[1]), "the camera sets were meant to reach different rows"
+    if os.environ.get("GSR_K8_SPARSE", "").startswith("0"):     # (the dense forms, which classify nothing: every bit set)
+        assert all(bool((m == -1).all()) for m in masks)
+    else:
+        assert not torch.equal(masks[0], masks[1]), "the camera sets were meant to reach different rows"
     arena.touch()
     assert not arena.zero_outside_ok()
 

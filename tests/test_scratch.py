@@ -2,7 +2,12 @@
 scratch_clean the caller keeps `partials` + `reach` between calls, hands them over ALL ZERO and gets them back all zero --
 no clear is launched; without it the library clears whatever it is given. Both protocols give the same gradients, for
 every form of K8 (the sparse and dense views kernels restore the scratch themselves; the scene forms and the single-view
-kernel with camera gradients get it cleared behind them)."""
+kernel get it cleared behind them). K >= 9 reaches the dense views kernel only under GSR_K8_SPARSE=0, which the library
+reads once per load: that case runs in a child process."""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 import torch
@@ -11,6 +16,7 @@ from tests.util import rel_scale, same_bits, settings_for, small_scene, tol_ok
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _all_scratch_zero(R):
@@ -40,9 +46,9 @@ def _legacy_bind_reach(gr, sc, k=0):
     gr.scratch_clean = 0
 
 
-@pytest.mark.parametrize("K,D,V,cam_grads", [(16, 3, 3, False), (4, 1, 2, False), (16, 3, 1, False), (16, 3, 1, True),
-                                             (9, 2, 4, False)])
-def test_scratch_is_returned_clean_and_protocols_agree(built_lib, monkeypatch, K, D, V, cam_grads):
+def _protocols_agree(K, D, V, cam_grads):
+    """K, D, V views of one scene, three calls per protocol: the scratch comes back all zero, and the two protocols
+    without the contract give the same gradients. Returns the contract's gradients (leaves, means2D[, viewmatrix])."""
     from dreamscene_amd import rasterizer as R, synth
     from dreamscene_amd.views import GaussianRasterizerViews
     dev = torch.device(DEV)
@@ -80,13 +86,47 @@ def test_scratch_is_returned_clean_and_protocols_agree(built_lib, monkeypatch, K
     clean = run()
     assert _all_scratch_zero(R) >= 1
     assert sum(float(np.abs(x).sum()) for x in clean) > 0
-    monkeypatch.setattr(R, "_bind_scratch", _legacy_bind)
-    legacy = run()
-    monkeypatch.setattr(R, "_bind_scratch", _legacy_bind_reach)
-    legacy_reach = run()
+    bind = R._bind_scratch
+    try:
+        R._bind_scratch = _legacy_bind
+        legacy = run()
+        R._bind_scratch = _legacy_bind_reach
+        legacy_reach = run()
+    finally:
+        R._bind_scratch = bind
     for a, b, c in zip(clean, legacy, legacy_reach):
         assert np.isfinite(b).all() and np.isfinite(c).all()
         assert tol_ok(a, b, atol=2e-6) and tol_ok(a, c, atol=2e-6)      # (fp32 atomics: order varies run to run)
+    return clean
+
+
+@pytest.mark.parametrize("K,D,V,cam_grads", [(16, 3, 3, False), (4, 1, 2, False), (16, 3, 1, False), (16, 3, 1, True),
+                                             (9, 2, 4, False)])
+def test_scratch_is_returned_clean_and_protocols_agree(built_lib, K, D, V, cam_grads):
+    _protocols_agree(K, D, V, cam_grads)
+
+
+DENSE_CASES = [(16, 3, 3, False), (16, 3, 1, False)]
+
+
+def _dense_child(path):
+    """the child of the test below, started with GSR_K8_SPARSE=0: the scenarios above, gradients to `path`"""
+    np.savez(path, **{f"c{c}_{i}": x for c, case in enumerate(DENSE_CASES) for i, x in enumerate(_protocols_agree(*case))})
+
+
+def test_dense_forms_keep_the_contract(built_lib, tmp_path):
+    """GSR_K8_SPARSE=0 (read once per library load, hence a fresh process): K = 16 then takes the dense views kernel for
+    3 views and the single-view kernel for one. Each keeps the contract and gives the gradients of the default form."""
+    path = tmp_path / "dense.npz"
+    cmd = [sys.executable, "-c", "import sys; from tests.test_scratch import _dense_child; _dense_child(sys.argv[1])",
+           str(path)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT,
+                       env=dict(os.environ, GSR_K8_SPARSE="0"))
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    dense = np.load(path)
+    for c, case in enumerate(DENSE_CASES):
+        for i, a in enumerate(_protocols_agree(*case)):
+            assert tol_ok(dense[f"c{c}_{i}"], a, atol=2e-6), (case, i)
 
 
 def test_scene_forms_clear_the_scratch_behind_them(built_lib):
