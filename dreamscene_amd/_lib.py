@@ -108,6 +108,30 @@ class GsrDispViews(C.Structure):
                 ("focal", C.c_float * GSR_MAX_DISP_VIEWS)]
 
 
+GSR_DENSIFY_TENSORS = 6
+GSR_DENSIFY_MAX_SPLIT = 8
+GSR_DENSIFY_SIZE_WORDS = 16
+GSR_DENSIFY_NAMES = ("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation")     # GSR_DENSIFY_XYZ ... in table order
+
+
+class GsrDensifyPlan(C.Structure):
+    _fields_ = [("P", C.c_int32), ("N", C.c_int32), ("densify", C.c_int32), ("use_screen_size", C.c_int32),
+                ("scaling", _f), ("opacity", _f), ("xyz_gradient_accum", _f), ("denom", _f), ("max_radii2D", _f),
+                ("max_grad", C.c_float), ("dense_threshold", C.c_float), ("min_opacity", C.c_float),
+                ("world_size_threshold", C.c_float), ("max_screen_size", C.c_float), ("child_divisor", C.c_float)]
+
+
+class GsrDensifyTensor(C.Structure):
+    _fields_ = [("src", _f), ("dst", _f), ("m1_src", _f), ("m1_dst", _f), ("m2_src", _f), ("m2_dst", _f),
+                ("width", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class GsrDensifyTable(C.Structure):
+    _fields_ = [("t", GsrDensifyTensor * GSR_DENSIFY_TENSORS), ("stat_src", _f * 3), ("stat_dst", _f * 3), ("noise", _f),
+                ("seed", C.c_uint64), ("P", C.c_int32), ("N", C.c_int32), ("n_survivors", C.c_int32), ("n_clones", C.c_int32),
+                ("n_children", C.c_int32), ("P_out", C.c_int32), ("zero_stats", C.c_int32), ("child_divisor", C.c_float)]
+
+
 # every symbol include/gsrast.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("gsr_adam_step", C.c_int, [C.POINTER(GsrAdamGroup), C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,
@@ -165,6 +189,10 @@ SYMBOLS = [
     ("gsr_tv_forward", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
                                  C.c_void_p]),
     ("gsr_tv_backward", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("gsr_densify_scratch_bytes", C.c_size_t, [C.c_int32, C.c_int32]),
+    ("gsr_densify_plan", C.c_int, [C.POINTER(GsrDensifyPlan), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("gsr_densify_plan_mask", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("gsr_densify_apply", C.c_int, [C.POINTER(GsrDensifyTable), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     ("gsr_backward", C.c_int, [C.POINTER(GsrView), C.POINTER(GsrGaussians), C.POINTER(GsrGeom), C.POINTER(GsrBinning),
                                C.POINTER(GsrImages), C.POINTER(GsrImageGrads), C.POINTER(GsrGrads), C.c_void_p,
                                C.c_void_p]),

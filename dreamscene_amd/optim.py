@@ -3,8 +3,9 @@
 Drop-in for the `torch.optim.Adam(l, lr=0.0, eps=1e-15)` the reference builds in `GaussianModel.training_setup`
 (gs_renderer.py:615-653): a torch.optim.Optimizer with the same `param_groups` (per-group "lr" and "name", which the
 reference's `update_learning_rate` mutates every step) and the same per-parameter `state` entries ("step", "exp_avg",
-"exp_avg_sq"), so the optimizer surgery of densification / pruning (`cat_tensors_to_optimizer`, `_prune_optimizer`,
-`replace_tensor_to_optimizer`) keeps working on it unchanged. Arithmetic: torch's single-tensor Adam, fp32.
+"exp_avg_sq"), so the optimizer surgery of densification / pruning -- `dreamscene_amd.densify.densify_and_prune / prune /
+prune_points`, or the reference's own `cat_tensors_to_optimizer`, `_prune_optimizer`, `replace_tensor_to_optimizer` -- works
+on it as on torch's. Arithmetic: torch's single-tensor Adam, fp32.
 No CPU fallback: parameters must live on a ROCm device."""
 from __future__ import annotations
 
