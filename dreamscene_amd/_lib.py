@@ -132,6 +132,14 @@ class GsrDensifyTable(C.Structure):
                 ("n_children", C.c_int32), ("P_out", C.c_int32), ("zero_stats", C.c_int32), ("child_divisor", C.c_float)]
 
 
+class GsrPlacement(C.Structure):
+    _fields_ = [("P", C.c_int32), ("K", C.c_int32), ("xyz", _f), ("scaling", _f), ("rotation", _f), ("opacity", _f),
+                ("features_dc", _f), ("features_rest", _f), ("xyz_out", _f), ("scaling_out", _f), ("rotation_out", _f),
+                ("features_rest_out", _f), ("rs", C.c_float * 9), ("t", C.c_float * 3), ("log_scale", C.c_float * 3),
+                ("q", C.c_float * 4), ("m1", C.c_float * 9), ("m2", C.c_float * 25), ("m3", C.c_float * 49),
+                ("ground", C.c_int32), ("bounds", _f), ("t_effective", _f)]
+
+
 # every symbol include/gsrast.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("gsr_adam_step", C.c_int, [C.POINTER(GsrAdamGroup), C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,
@@ -193,6 +201,8 @@ SYMBOLS = [
     ("gsr_densify_plan", C.c_int, [C.POINTER(GsrDensifyPlan), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("gsr_densify_plan_mask", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("gsr_densify_apply", C.c_int, [C.POINTER(GsrDensifyTable), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    ("gsr_place_scratch_bytes", C.c_size_t, [C.c_int32]),
+    ("gsr_place", C.c_int, [C.POINTER(GsrPlacement), C.c_void_p, C.c_size_t, C.c_void_p]),
     ("gsr_backward", C.c_int, [C.POINTER(GsrView), C.POINTER(GsrGaussians), C.POINTER(GsrGeom), C.POINTER(GsrBinning),
                                C.POINTER(GsrImages), C.POINTER(GsrImageGrads), C.POINTER(GsrGrads), C.c_void_p,
                                C.c_void_p]),

@@ -563,6 +563,50 @@ int gsr_densify_plan_mask(const uint8_t* mask, int32_t P, void* scratch, size_t 
                           int32_t* sizes_host, void* stream);
 int gsr_densify_apply(const GsrDensifyTable* table, const void* scratch, size_t scratch_bytes, int32_t* src, void* stream);
 
+/* ---- object placement: SceneGaussian.add_objects_to_scene (scene_gaussian.py:318-427; dreamscene_amd/compose.py; SEMANTICS.md
+ * "Object placement") ---------------------------------------------------------------------------------------------------------------
+ * One trained object moved into the scene frame by a rotation R, a per-axis scale S and a translation, for K = 1, 4, 9 or 16 SH
+ * coefficients per colour:
+ *   xyz'      = fl32(R S x) + T       rs = R S rounded once to fp32; ((rs0 x0 + rs1 x1) + rs2 x2) + T, one rounding per operator;
+ *                                     T = t, or with ground != 0 T.z = t.z - min over the rows of fl32(R S x).z (the object stands
+ *                                     on z = t.z; one fp32 subtraction on the device, no host read);
+ *   scaling'  = scaling + log_scale   one fp32 add per entry;
+ *   rotation' = q (x) rotation        the raw Hamilton product, real part first, not normalised;
+ *   f_rest'   [P,K-1,3]: band l = 1, 2, 3 (coefficients [0,3), [3,8), [8,15)) multiplied on the COEFFICIENT axis,
+ *                                     k'[j][c] = sum_i k[i][c] m_l[i][j] (row-major m1 [3][3], m2 [5][5], m3 [7][7], the same for
+ *                                     the three colours c), summed in index order; only the bands K holds are touched.
+ * features_dc and opacity are not read (NULL is accepted); they are listed so that an output overlapping them is refused.
+ * gsr_place  two launches on `stream`, no host synchronisation, no allocation (capturable): the box of fl32(R S x) per block into
+ *            scratch, then every row. bounds[6] = (min xyz', max xyz') of the rows written; t_effective (NULL or 3 floats) = the T
+ *            that was added. NaN coordinates do not enter the box. An output may be its own input (in place); an output that
+ *            overlaps anything else the call touches, K outside {1, 4, 9, 16}, a NULL or not 16-byte aligned pointer and a
+ *            scratch smaller than gsr_place_scratch_bytes(P) (16-byte aligned; 0: P is not accepted) return GSR_EINVAL before
+ *            any HIP call. P = 0 is valid and launches nothing. */
+typedef struct GsrPlacement {
+  int32_t P;                       /* rows                                                       */
+  int32_t K;                       /* SH coefficients per colour: 1, 4, 9 or 16                  */
+  const float* xyz;                /* [P,3]                                                      */
+  const float* scaling;            /* [P,3] log                                                  */
+  const float* rotation;           /* [P,4] (w, x, y, z)                                         */
+  const float* opacity;            /* [P,1] not read                                             */
+  const float* features_dc;        /* [P,1,3] not read                                           */
+  const float* features_rest;      /* [P,K-1,3] (unused at K = 1)                                */
+  float* xyz_out;
+  float* scaling_out;
+  float* rotation_out;
+  float* features_rest_out;
+  float rs[9];                     /* R S, row-major                                             */
+  float t[3];                      /* the centre                                                 */
+  float log_scale[3];              /* log of the per-axis scale, formed in double, rounded once  */
+  float q[4];                      /* the quaternion of R (w, x, y, z)                           */
+  float m1[9], m2[25], m3[49];     /* the band matrices, Y_i(R^T d) = sum_j m_l[i][j] Y_j(d)     */
+  int32_t ground;                  /* != 0: T.z = t.z - min z                                    */
+  float* bounds;                   /* [6] out                                                    */
+  float* t_effective;              /* [3] out, or NULL                                           */
+} GsrPlacement;
+size_t gsr_place_scratch_bytes(int32_t P);
+int gsr_place(const GsrPlacement* placement, void* scratch, size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
