@@ -18,6 +18,7 @@ ARCH = "gfx950"
 SOURCES = {
     "api.hip": [],
     "preprocess.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
+    "preprocess_bwd.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
     "binning.hip": ["-ffp-contract=off"],
     "render.hip": ["-fno-slp-vectorize"],
     "knn.hip": ["-ffp-contract=off"],
@@ -52,8 +53,8 @@ def build(force: bool = False, verbose: bool = False, extra_flags=(), out: str =
     cc = hipcc()
     objdir = objdir or os.path.join(HERE, "_obj")
     os.makedirs(objdir, exist_ok=True)
-    headers = [os.path.join(CSRC, "gsr_common.h"), os.path.join(CSRC, "radix_sort.h"),
-               os.path.join(ROOT, "include", "gsrast.h"), os.path.abspath(__file__)]
+    headers = sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h"))
+    headers += [os.path.join(ROOT, "include", "gsrast.h"), os.path.abspath(__file__)]
     jobs = []
     for src, flags in SOURCES.items():
         s = os.path.join(CSRC, src)

@@ -3,7 +3,7 @@
 
 thread_local int gsr_tls_hip_error = 0;
 
-// stage launchers (preprocess.hip, binning.hip, render.hip)
+// stage launchers (preprocess.hip, preprocess_bwd.hip, binning.hip, render.hip)
 int gsr_launch_preprocess(const GsrView&, const GsrGaussians&, GsrGeom&, hipStream_t);
 bool gsr_preprocess_views_supported(const GsrView&, const GsrGaussians&);
 int gsr_launch_preprocess_views(int n_views, const GsrView* views, const GsrGaussians* gs, GsrGeom* geoms, hipStream_t);

@@ -1,4 +1,4 @@
-"""-m gpu: K8's sparse form (csrc/preprocess.hip, k_preprocess_bwd_views<K, PVS, REACHED>). A workgroup of 256
+"""-m gpu: K8's sparse form (csrc/preprocess_bwd.hip, k_preprocess_bwd_views<K, PVS, REACHED>). A workgroup of 256
 Gaussians of which K7 reached at most 128 compacts them and runs the chain rule on those only; the others get zeros
 from coalesced clears. The scene below puts all three cases side by side -- workgroups nothing reached (opacity below
 1/255: visible, never blended), workgroups mostly reached (they stay dense) and mixed ones -- and the gradients are
