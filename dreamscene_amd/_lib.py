@@ -140,6 +140,14 @@ class GsrPlacement(C.Structure):
                 ("ground", C.c_int32), ("bounds", _f), ("t_effective", _f)]
 
 
+GSR_MAX_FRAME_VIEWS = 16
+
+
+class GsrFrameViews(C.Structure):
+    _fields_ = [("n_views", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("reserved_", C.c_int32),
+                ("image", _f * GSR_MAX_FRAME_VIEWS), ("depth_alpha", _f * GSR_MAX_FRAME_VIEWS)]
+
+
 # every symbol include/gsrast.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("gsr_adam_step", C.c_int, [C.POINTER(GsrAdamGroup), C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,
@@ -203,6 +211,8 @@ SYMBOLS = [
     ("gsr_densify_apply", C.c_int, [C.POINTER(GsrDensifyTable), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     ("gsr_place_scratch_bytes", C.c_size_t, [C.c_int32]),
     ("gsr_place", C.c_int, [C.POINTER(GsrPlacement), C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("gsr_frames_scratch_bytes", C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    ("gsr_frames_quantize", C.c_int, [C.POINTER(GsrFrameViews), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("gsr_backward", C.c_int, [C.POINTER(GsrView), C.POINTER(GsrGaussians), C.POINTER(GsrGeom), C.POINTER(GsrBinning),
                                C.POINTER(GsrImages), C.POINTER(GsrImageGrads), C.POINTER(GsrGrads), C.c_void_p,
                                C.c_void_p]),

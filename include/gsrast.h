@@ -607,6 +607,33 @@ typedef struct GsrPlacement {
 size_t gsr_place_scratch_bytes(int32_t P);
 int gsr_place(const GsrPlacement* placement, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- frame export: the uint8 tail of video_inference / scene_video_inference / scene_cams_record (training/object_trainer.py:
+ * 81-118, training/scene_trainer.py:261-340; dreamscene_amd/frames.py; SEMANTICS.md "Frame export") -----------------------------
+ * Up to GSR_MAX_FRAME_VIEWS rendered views of one size, each its own image [3,H,W] and (optionally) depth_alpha [2,H,W] as the
+ * forward returns them (no stacking), to interleaved bytes:
+ *   rgb   [F,H,W,3] uint8 = rint(fl32(clamp(x, 0, 1) * 255)), round half to even (numpy's round);
+ *   depth [F,H,W,1] uint8 = the same chain on fl32(d / M), d = plane 0 of depth_alpha, M = that frame's own maximum of the plane,
+ *                           a correctly rounded fp32 division; NULL: not wanted.
+ * Inputs are finite (precondition). A NaN of the chain -- only 0 / 0 of an all-zero depth frame -- gives byte 0.
+ * gsr_frames_quantize  depth != NULL: two launches (the per-block maxima into scratch, then every block reduces its frame's
+ *                      maxima and writes the bytes); depth == NULL: one launch, depth_alpha and scratch are not read. Enqueued on
+ *                      `stream`, no allocation, no host synchronisation, no atomics (capturable; the same bytes on every run).
+ *                      Plane pointers 4-byte aligned (16-byte aligned planes with H*W % 4 == 0 are read 16 bytes at a time); rgb
+ *                      and depth need no alignment. scratch: gsr_frames_scratch_bytes(F, H, W) bytes, 16-byte aligned (0: the
+ *                      shape is not accepted); too small: GSR_ESCRATCH. Bad shapes and NULL pointers: GSR_EINVAL before any HIP
+ *                      call. */
+#define GSR_MAX_FRAME_VIEWS 16
+typedef struct GsrFrameViews {
+  int32_t n_views;                                   /* 1..GSR_MAX_FRAME_VIEWS                                  */
+  int32_t height, width;
+  int32_t reserved_;
+  const float* image[GSR_MAX_FRAME_VIEWS];           /* view k: [3,H,W]                                         */
+  const float* depth_alpha[GSR_MAX_FRAME_VIEWS];     /* view k: [2,H,W]; only plane 0 is read; unused without depth */
+} GsrFrameViews;
+size_t gsr_frames_scratch_bytes(int32_t n_views, int32_t height, int32_t width);
+int gsr_frames_quantize(const GsrFrameViews* views, uint8_t* rgb, uint8_t* depth, void* scratch, size_t scratch_bytes,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif
