@@ -1,5 +1,7 @@
 """-m gpu: seeded random configurations (sizes, image shapes, cameras, scale ranges, SH strides, degenerate inputs) through
-the same bars as tests/test_gpu_parity.py: integer artefacts bit-exact against the C oracle, image / gradients <= 1e-5."""
+the same bars as tests/test_gpu_parity.py: integer artefacts bit-exact against the C oracle, image / gradients <= 1e-5.
+This file moves in GAUSSIAN space under three orbit poses (no roll, tanfov < 1, scale_modifier 1.0); camera and settings space
+-- roll, FoV 0.2 ... 2.2, independent tanfovy, scale_modifier 0.25 ... 3, in every kernel form -- is tests/test_fuzz_cameras.py."""
 import numpy as np
 import pytest
 from tests.test_gpu_parity import _check_forward, _grad_check, _run_hip

@@ -19,9 +19,9 @@ def _to_dev(g):
     return {k: torch.tensor(v, device=DEV) for k, v in g.items()}
 
 
-def _run_hip(g, cam, bg, D, score=False, want_keys=True, rc=None, seg_len=None, **over):
+def _run_hip(g, cam, bg, D, score=False, want_keys=True, rc=None, seg_len=None, scale_modifier=1.0, **over):
     from dreamscene_amd import rasterizer as R
-    s = settings_for(cam, bg, D, DEV, score_flag=score)
+    s = settings_for(cam, bg, D, DEV, score_flag=score, scale_modifier=scale_modifier)
     t = _to_dev(g)
     kw = dict(shs=t.get("shs"), colors_precomp=t.get("colors_precomp"), scales=t.get("scales"),
               rotations=t.get("rotations"), cov3D_precomp=t.get("cov3D_precomp"))
@@ -66,16 +66,16 @@ def test_forward_vs_c_oracle(built_lib, c_oracle, D, K):
     _check_forward(out, f, 2000)
 
 
-def _grad_check(g, cam, bg, D, c_oracle, colors=False, cov=False, seed=0, tol=TOL, rc=None):
+def _grad_check(g, cam, bg, D, c_oracle, colors=False, cov=False, seed=0, tol=TOL, rc=None, scale_modifier=1.0):
     from dreamscene_amd import rasterizer as R, synth
     P = g["means3D"].shape[0]
     K = g["shs"].shape[1] if "shs" in g else 0
     H, W = cam.image_height, cam.image_width
     gi, gda = synth.upstream_grads(H, W, seed)
-    out, st = _run_hip(g, cam, bg, D, want_keys=False, rc=rc)
+    out, st = _run_hip(g, cam, bg, D, want_keys=False, rc=rc, scale_modifier=scale_modifier)
     o = R.rasterize_backward_raw(st, torch.tensor(gi, device=DEV), torch.tensor(gda, device=DEV), cam_grads=True)
     torch.cuda.synchronize()
-    v = oracle_view(c_oracle, cam, P, K, D, bg)
+    v = oracle_view(c_oracle, cam, P, K, D, bg, scale_modifier=scale_modifier)
     f = c_oracle.forward(v, g["means3D"], g["opacities"], shs=g.get("shs"), colors_precomp=g.get("colors_precomp"),
                          scales=g.get("scales"), rotations=g.get("rotations"), cov3D_precomp=g.get("cov3D_precomp"))
     b = c_oracle.backward(v, f, gi, gda, g["means3D"], shs=g.get("shs"), scales=g.get("scales"),

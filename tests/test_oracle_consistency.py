@@ -5,10 +5,11 @@ import numpy as np
 import pytest
 import torch
 
-from tests.util import err, oracle_view, rel_scale, small_scene
+from tests.util import CAMERA_FUZZ_SEEDS, err, oracle_view, random_settings_config, rel_scale, small_scene
 
 
-def _torch_run(g, cam, bg, D, dt=torch.float64, score=False, score_mode=0, cam_grad=True, gi=None, gda=None, tile_window=None):
+def _torch_run(g, cam, bg, D, dt=torch.float64, score=False, score_mode=0, cam_grad=True, gi=None, gda=None, tile_window=None,
+               scale_modifier=1.0):
     from oracle import torch_oracle as TO
     P = g["means3D"].shape[0]
     t = {k: torch.tensor(v, dtype=dt, requires_grad=True) for k, v in g.items()}
@@ -16,8 +17,8 @@ def _torch_run(g, cam, bg, D, dt=torch.float64, score=False, score_mode=0, cam_g
     vm = torch.tensor(cam.world_view_transform, dtype=dt, requires_grad=cam_grad)
     pm = torch.tensor(cam.full_proj_transform, dtype=dt, requires_grad=cam_grad)
     cp = torch.tensor(cam.camera_center, dtype=dt, requires_grad=cam_grad)
-    s = TO.Settings(cam.image_height, cam.image_width, cam.tanfovx, cam.tanfovy, torch.tensor(bg, dtype=dt), 1.0, vm, pm,
-                    D, cp, False, score)
+    s = TO.Settings(cam.image_height, cam.image_width, cam.tanfovx, cam.tanfovy, torch.tensor(bg, dtype=dt), scale_modifier,
+                    vm, pm, D, cp, False, score)
     res, aux = TO.rasterize(t["means3D"], m2d, t["opacities"], shs=t.get("shs"), colors_precomp=t.get("colors_precomp"),
                             scales=t.get("scales"), rotations=t.get("rotations"), cov3D_precomp=t.get("cov3D_precomp"),
                             settings=s, score_mode=score_mode, return_aux=True, tile_window=tile_window)
@@ -64,6 +65,48 @@ def test_forward_backward_c_vs_torch(c_oracle, D, K, seed):
     for tk, ck in pairs:
         a, c = r["grads"][tk], b[ck]
         assert err(a, c) <= 1e-5 * rel_scale(a), tk
+
+
+def _c_vs_float64(c_oracle, g, cam, bg, P, K, D, mod, seed):
+    """-> (forward of the C oracle, {tensor: error against float64 autograd / its own largest entry})."""
+    from dreamscene_amd import synth
+    H, W = cam.image_height, cam.image_width
+    gi, gda = synth.upstream_grads(H, W, seed)
+    r = _torch_run(g, cam, bg, D, gi=gi, gda=gda, scale_modifier=mod)
+    v = oracle_view(c_oracle, cam, P, K, D, bg, scale_modifier=mod)
+    f = c_oracle.forward(v, g["means3D"], g["opacities"], shs=g["shs"], scales=g["scales"], rotations=g["rotations"])
+    b = c_oracle.backward(v, f, gi, gda, g["means3D"], shs=g["shs"], scales=g["scales"], rotations=g["rotations"],
+                          cam_grads=True)
+    assert np.array_equal(f["radii"], r["radii"])
+    assert np.array_equal(f["point_list"], r["aux"]["binning"].point_list)
+    assert np.array_equal(f["keys"] >> np.uint64(32), r["aux"]["binning"].keys >> np.uint64(32))
+    assert np.array_equal(f["ranges"], r["aux"]["binning"].ranges)
+    assert np.array_equal(f["n_contrib"], r["aux"]["n_contrib"])
+    rep = dict(image=err(f["image"], r["img"]), depth_alpha=err(f["depth_alpha"], r["da"]))
+    for tk, ck in [("means3D", "dL_dmeans3D"), ("scales", "dL_dscales"), ("rotations", "dL_drotations"),
+                   ("opacities", "dL_dopacity"), ("shs", "dL_dshs"), ("means2D", "dL_dmeans2D"), ("view", "dL_dview"),
+                   ("proj", "dL_dproj"), ("campos", "dL_dcampos")]:
+        a = r["grads"][tk]
+        rep[tk] = err(a, np.asarray(b[ck]).reshape(a.shape)) / rel_scale(a)
+    return f, rep
+
+
+@pytest.mark.parametrize("seed", CAMERA_FUZZ_SEEDS)
+def test_random_cameras_and_scale_modifier_c_vs_float64(c_oracle, seed):
+    """The seeds of tests/test_fuzz_cameras.py (rolled look-at cameras, FoV 0.2 ... 2.2, tanfovy independent of tanfovx,
+    scale_modifier 0.25 ... 3): the C oracle that arbitrates them on the GPU is within test_forward_backward_c_vs_torch's
+    bars of float64 autograd on every one of them, and every one of them renders something."""
+    g, cam, bg, P, K, D, mod = random_settings_config(seed)
+    f, rep = _c_vs_float64(c_oracle, g, cam, bg, P, K, D, mod, seed)
+    n_vis = int((f["radii"] > 0).sum())
+    print(f"[camera fuzz seed {seed}] P {P} K {K} D {D} {cam.image_height}x{cam.image_width} tanfov {cam.tanfovx:.3f} "
+          f"{cam.tanfovy:.3f} mod {mod}: visible {n_vis}, N {f['N']}; " + " ".join(f"{k} {v:.1e}" for k, v in rep.items()))
+    if P >= 65:
+        assert n_vis >= 16 and f["N"] >= 100, (n_vis, f["N"])
+    assert rep.pop("image") <= 2e-6
+    assert rep.pop("depth_alpha") <= 2e-5
+    for tk, e in rep.items():
+        assert e <= 1e-5, (tk, e)
 
 
 def test_needles_vs_float64(c_oracle):
