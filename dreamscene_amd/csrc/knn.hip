@@ -164,7 +164,9 @@ __global__ void k_knn_init(int* __restrict__ bbox) {
 extern "C" size_t gsr_knn_scratch_bytes(int32_t n) {
   const uint64_t m = n > 0 ? (uint64_t)n : 1;
   const size_t cells = (size_t)kMaxR * kMaxR * kMaxR;
-  const uint64_t r = (uint64_t)cbrt(0.5 * (double)m) + 1;
+  // room for (R + 1)^3 cells whichever way cbrt (here) and cbrtf (on the device) round at n = 2 k^3: cbrt(k^3) may be just
+  // below k, so R is this truncation or one more
+  const uint64_t r = (uint64_t)cbrt(0.5 * (double)m) + 2;
   const size_t rc = (size_t)std::min<uint64_t>(r * r * r, cells);
   return 4 * align256(m * 4) + sort_hist_bytes(m, kItemsSmall, kOsItemsSmall) + align256(256 * 4) +
          align256(rc * 8) + 256 + 1024;

@@ -5,8 +5,10 @@
 // go through ONE launch: a table of (param, grad, exp_avg, exp_avg_sq, numel, lr) in the kernel arguments, one
 // pass over memory (16 bytes read + 12 written per element, + 4 when the gradient is cleared in the same pass).
 // The arithmetic is torch's single-tensor Adam (torch/optim/adam.py, no amsgrad / weight decay / maximize), one
-// rounding per operator (this file is built with -ffp-contract=off):
-//   m <- m + (g - m) (1 - beta1);  v <- v beta2 + (1 - beta2) g g
+// rounding per operator (this file is built with -ffp-contract=off) except where ATen itself fuses: lerp_ is
+// fma(weight, end - self, self) and addcmul_ is fma(value * t1, t2, self) in torch's CPU kernels, so both moments
+// carry torch-fp32's bits (SEMANTICS.md, "FusedAdam"); the parameter differs by the association of addcdiv_ only:
+//   m <- fma(1 - beta1, g - m, m);  v <- fma((1 - beta2) g, g, v beta2)
 //   p <- p - (lr / (1 - beta1^t)) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
 #include "gsr_common.h"
 
@@ -27,8 +29,8 @@ constexpr int kAdamPerBlock = 256 * 4;
 
 __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, float step_size, float w1, float beta2,
                                          float w2, float bc2_sqrt, float eps) {
-  m = m + (g - m) * w1;
-  v = v * beta2 + (w2 * g) * g;
+  m = fmaf(w1, g - m, m);
+  v = fmaf(w2 * g, g, v * beta2);
   const float denom = sqrtf(v) / bc2_sqrt + eps;
   p = p - step_size * (m / denom);
 }

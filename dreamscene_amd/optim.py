@@ -37,7 +37,11 @@ class FusedAdam(torch.optim.Optimizer):
         """grads: optional gradient tensors, one per parameter in param_groups order (e.g. views of a GradArena),
         instead of `p.grad`. zero_grad: clear the gradients inside the same pass over memory (persistent buffers such as
         an arena). set_to_none: drop the `.grad` tensors after the step (like optimizer.zero_grad(set_to_none=True)): the
-        next backward's gradients then become `.grad` without an accumulation pass."""
+        next backward's gradients then become `.grad` without an accumulation pass.
+        A non-contiguous gradient (a slice of a shared buffer, a transposed `.grad`) is accepted: the kernel reads a
+        contiguous copy, and with zero_grad the caller's own tensor is cleared on the same stream after the launch, so
+        the buffer is zero afterwards exactly as a contiguous one is.
+        Every parameter and gradient is validated before any state is touched: a refused call changes nothing."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -46,10 +50,8 @@ class FusedAdam(torch.optim.Optimizer):
         flat = [(g, p) for g in self.param_groups for p in g["params"]]
         if grads is not None and len(grads) != len(flat):
             raise ValueError("grads must list one tensor (or None) per parameter")
-        # parameters that share (betas, eps, step) go into one launch
-        batches = {}
-        keep = []
-        updated = []
+        # validate everything first: a refused call leaves every `step` and every tensor as it was
+        todo = []
         for k, (group, p) in enumerate(flat):
             gr = grads[k] if grads is not None else p.grad
             if gr is None:
@@ -60,23 +62,37 @@ class FusedAdam(torch.optim.Optimizer):
                 raise ValueError("FusedAdam parameters must be contiguous fp32")
             if gr.dtype != torch.float32 or gr.shape != p.shape or gr.device != p.device:
                 raise ValueError("gradient does not match its parameter")
+            if p.data_ptr() % 16 or (gr.is_contiguous() and gr.data_ptr() % 16):
+                raise ValueError("FusedAdam tensors must be 16-byte aligned")
+            todo.append((group, p, gr))
+        # parameters that share (betas, eps, step) go into one launch
+        batches = {}
+        ready = []
+        keep = []
+        updated = []
+        clear = []      # the callers' non-contiguous gradients: the kernel clears only its contiguous copy
+        for group, p, gr in todo:
             if not gr.is_contiguous():
+                if zero_grad:
+                    clear.append(gr)
                 gr = gr.contiguous()
             st = self._state_for(p)
-            st["step"] += 1
-            step = int(st["step"].item())
             for name in ("exp_avg", "exp_avg_sq"):
                 if not st[name].is_contiguous():
                     st[name] = st[name].contiguous()
-            key = (p.device, group["betas"], float(group["eps"]), step)
-            e = L.GsrAdamGroup()
-            e.param, e.grad, e.exp_avg, e.exp_avg_sq = p.data_ptr(), gr.data_ptr(), st["exp_avg"].data_ptr(), \
-                st["exp_avg_sq"].data_ptr()
-            e.numel, e.lr = p.numel(), float(group["lr"])
-            if any(ptr % 16 for ptr in (e.param, e.grad, e.exp_avg, e.exp_avg_sq)):
+            ptrs = (p.data_ptr(), gr.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr())
+            if any(ptr % 16 for ptr in ptrs):          # (an empty tensor's pointer is 0)
                 raise ValueError("FusedAdam tensors must be 16-byte aligned")
-            batches.setdefault(key, []).append(e)
+            e = L.GsrAdamGroup()
+            e.param, e.grad, e.exp_avg, e.exp_avg_sq = ptrs
+            e.numel, e.lr = p.numel(), float(group["lr"])
+            ready.append((group, p, st, e))
             keep.append(gr)
+        for group, p, st, e in ready:
+            st["step"] += 1
+            step = int(st["step"].item())
+            key = (p.device, group["betas"], float(group["eps"]), step)
+            batches.setdefault(key, []).append(e)
             updated.append(p)
         for (dev, betas, eps, step), entries in batches.items():
             stream = torch.cuda.current_stream(dev).cuda_stream
@@ -86,6 +102,8 @@ class FusedAdam(torch.optim.Optimizer):
                     arr = (L.GsrAdamGroup * len(chunk))(*chunk)
                     L.check(lib.gsr_adam_step(arr, len(chunk), step, betas[0], betas[1], eps, int(zero_grad), stream),
                             "gsr_adam_step")
+        for gr in clear:
+            gr.zero_()
         # the launch wrote the parameters through raw pointers: tell autograd's version counters (the rasterizer's
         # "inputs unchanged since ..." checks -- rasterizer._check_versions, _SideStreams -- rely on them)
         for p in updated:
