@@ -20,7 +20,8 @@ SOURCES = {
     "preprocess.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
     "preprocess_bwd.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
     "binning.hip": ["-ffp-contract=off"],
-    "render.hip": ["-fno-slp-vectorize"],
+    "render_fwd.hip": ["-fno-slp-vectorize"],
+    "render_bwd.hip": ["-fno-slp-vectorize"],
     "knn.hip": ["-ffp-contract=off"],
     "optim.hip": ["-ffp-contract=off"],
     "exchange.hip": [],

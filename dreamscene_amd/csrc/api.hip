@@ -1,32 +1,8 @@
 // api.hip -- the extern "C" boundary declared in include/gsrast.h.
 #include "gsr_common.h"
+#include "gsr_launch.h"
 
 thread_local int gsr_tls_hip_error = 0;
-
-// stage launchers (preprocess.hip, preprocess_bwd.hip, binning.hip, render.hip)
-int gsr_launch_preprocess(const GsrView&, const GsrGaussians&, GsrGeom&, hipStream_t);
-bool gsr_preprocess_views_supported(const GsrView&, const GsrGaussians&);
-int gsr_launch_preprocess_views(int n_views, const GsrView* views, const GsrGaussians* gs, GsrGeom* geoms, hipStream_t);
-bool gsr_preprocess_bwd_views_supported(const GsrView&, const GsrGaussians&, const GsrGrads&);
-int gsr_launch_preprocess_bwd(int n_views, const GsrView* views, const GsrGaussians* gs, const GsrGeom* geoms,
-                              const GsrGrads* outs, hipStream_t, bool* restored);
-int gsr_launch_depth_order(GsrGeom&, const GsrView&, hipStream_t, GsrProfile*, int batch, size_t bstride,
-                           uint64_t* n_pairs_all, bool early);
-uint64_t* gsr_pair_counts(const GsrGeom&, int32_t P);
-bool gsr_uses_columns(const GsrView&);
-int gsr_launch_binning(const GsrView&, const GsrGeom&, uint64_t cap, const uint64_t* n_dev, const uint64_t* n_dev_vis,
-                       GsrBinning&, hipStream_t, GsrProfile*);
-int gsr_launch_binning_batch(int n, const GsrView* views, const GsrGeom* geoms, uint64_t cap, GsrBinning* bs, hipStream_t,
-                             GsrProfile*);
-int gsr_launch_render_fwd(const GsrView&, const GsrGeom&, const GsrBinning&, GsrImages&, hipStream_t, GsrProfile*);
-int gsr_launch_render_fwd_views(int n, const GsrView* views, const GsrGeom* geoms, const GsrBinning* bs, GsrImages* imgs,
-                                hipStream_t, GsrProfile*);
-int gsr_launch_render_bwd_views(int n, const GsrView* views, const GsrGeom* geoms, const GsrBinning* bs,
-                                const GsrImages* imgs, const GsrImageGrads* igs, GsrGrads* outs, hipStream_t, GsrProfile*);
-int gsr_launch_work_order_fwd(int n, const GsrView* views, const GsrBinning* bs, const GsrImages* imgs, hipStream_t);
-int gsr_launch_work_order_bwd(int n, const GsrView* views, const GsrBinning* bs, const GsrImages* imgs, hipStream_t);
-int gsr_launch_render_bwd(const GsrView&, const GsrGeom&, const GsrBinning&, const GsrImages&, const GsrImageGrads&,
-                          GsrGrads&, hipStream_t, GsrProfile*);
 
 namespace {
 
@@ -192,8 +168,6 @@ int gsr_pack_views(int32_t n_views, const GsrView* views, float* packed, void* s
   return GSR_OK;
 }
 
-static uint64_t* n_pairs_device(const GsrGeom* geom, int32_t P) { return gsr_pair_counts(*geom, P); }
-
 static int forward_project(const GsrView* v, const GsrGaussians* g, GsrGeom* geom, uint64_t* n_pairs_host,
                            void* stream_, GsrProfile* prof, bool sync) {
   int rc = check_view(v);
@@ -215,7 +189,7 @@ static int forward_project(const GsrView* v, const GsrGaussians* g, GsrGeom* geo
     rc = gsr_launch_preprocess(*v, *g, *geom, stream);
     if (rc) return rc;
   }
-  uint64_t* n_dev = n_pairs_device(geom, v->P);
+  uint64_t* n_dev = gsr_pair_counts(*geom, v->P);
   // async + column path: n_pairs_host is page-locked and k_col_plan stores N there itself (no copy operation)
   const bool direct = !sync && gsr_uses_columns(*v);
   rc = gsr_launch_depth_order(*geom, *v, stream, prof, 1, 0, direct ? n_pairs_host : nullptr, /*early=*/true);
@@ -309,8 +283,8 @@ static int check_render(const GsrView* v, const GsrGeom* geom, uint64_t n_pairs,
 static int render_binning(const GsrView* v, const GsrGeom* geom, uint64_t n_pairs, GsrBinning* b, hipStream_t stream,
                           GsrProfile* prof) {
   if (v->P == 0) n_pairs = 0;
-  const uint64_t* n_dev = (b->count_on_device && v->P > 0) ? n_pairs_device(geom, v->P) : nullptr;
-  const uint64_t* n_vis = v->P > 0 ? n_pairs_device(geom, v->P) + 1 : nullptr;
+  const uint64_t* n_dev = (b->count_on_device && v->P > 0) ? gsr_pair_counts(*geom, v->P) : nullptr;
+  const uint64_t* n_vis = v->P > 0 ? gsr_pair_counts(*geom, v->P) + 1 : nullptr;
   return gsr_launch_binning(*v, *geom, n_pairs, n_dev, n_vis, *b, stream, prof);
 }
 
@@ -324,7 +298,7 @@ int gsr_forward_render(const GsrView* v, const GsrGeom* geom, uint64_t n_pairs, 
   if (rc) return rc;
   rc = gsr_launch_work_order_fwd(1, v, b, img, stream);
   if (rc) return rc;
-  return gsr_launch_render_fwd(*v, *geom, *b, *img, stream, prof);
+  return gsr_launch_render_fwd_views(1, v, geom, b, img, stream, prof);
 }
 
 int gsr_forward_render_batch(int32_t n_views, const GsrView* views, const GsrGeom* geoms, uint64_t n_pairs,
@@ -366,7 +340,7 @@ int gsr_forward_render_batch(int32_t n_views, const GsrView* views, const GsrGeo
               views[k].score_mode == views[0].score_mode;
   if (uniform) return gsr_launch_render_fwd_views(n_views, views, geoms, bs, imgs, stream, prof);
   for (int k = 0; k < n_views; ++k) {
-    rc = gsr_launch_render_fwd(views[k], geoms[k], bs[k], imgs[k], stream, prof);
+    rc = gsr_launch_render_fwd_views(1, &views[k], &geoms[k], &bs[k], &imgs[k], stream, prof);
     if (rc) return rc;
   }
   return GSR_OK;
@@ -422,7 +396,7 @@ static int backward_render(const GsrView* v, const GsrGeom* geom, const GsrBinni
     const int rc = clear_scratch(v, out, stream, clear_partials);
     if (rc) return rc;
   }
-  return gsr_launch_render_bwd(*v, *geom, *b, *img, *ig, *out, stream, prof);
+  return gsr_launch_render_bwd_views(1, v, geom, b, img, ig, out, stream, prof);
 }
 
 int gsr_backward(const GsrView* v, const GsrGaussians* g, const GsrGeom* geom, const GsrBinning* b,

@@ -27,6 +27,7 @@
 // memory and clamps it to the capacity of the caller's buffers, so the whole forward can be enqueued without a
 // host round trip; the host checks N against the capacity afterwards (gsrast.h, gsr_forward_render).
 #include "gsr_common.h"
+#include "gsr_launch.h"
 #include "radix_sort.h"
 
 namespace {

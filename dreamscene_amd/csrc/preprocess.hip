@@ -15,6 +15,7 @@
 // (depth bits, radius, tile rectangle) rounds exactly once, in the order written -- the same order as
 // oracle/gsr_oracle.c -- which is what makes radii / tile counts / sort keys bit-exact against the oracle.
 #include "gsr_project.h"
+#include "gsr_launch.h"
 
 namespace {
 
@@ -68,7 +69,7 @@ __device__ __forceinline__ void proj_footprint(const ViewConst& vc, float px, fl
 }
 // Level of the conic form below which a splat can pass the alpha >= 1/255 gate: sigma exp(-q/2) >= 1/255 <=>
 // q = d^T Conic d <= 2 ln(255 sigma) =: tau (slightly inflated). Used only to skip (pixel block, splat) pairs that
-// cannot contribute (render.hip); negative = the splat contributes nowhere. Not part of any parity artefact.
+// cannot contribute (gsr_render.h, block_mask_t); negative = the splat contributes nowhere. Not part of any parity artefact.
 __device__ __forceinline__ float splat_tau(float opac) {
   return (opac * 255.0f > 1.0f) ? 2.0f * logf(opac * 255.0f) * 1.0001f + 0.001f : -1.f;
 }

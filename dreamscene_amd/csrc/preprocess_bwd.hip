@@ -1,6 +1,7 @@
 // preprocess_bwd.hip -- K8, the backward of K1 (preprocess.hip; kernel forms, traffic and the -ffp-contract=off build: see
 // there), gfx950. K8 recomputes K1's projection with the statements of gsr_project.h: same order, same values.
 #include "gsr_project.h"
+#include "gsr_launch.h"
 #include <cstdlib>
 
 namespace {
@@ -106,7 +107,7 @@ __device__ __forceinline__ void geom_backward(const ViewConst& vc, const Ewa& e,
   // (2) K7's sums -> dL/d(ndc xy) and dL/dcov2D. With d = centre - pixel, (u, v) = -conic d and q = dL/dG G per pixel:
   // S1 = sum q u, S2 = sum q v are dL/d(pixel centre); dL/dSigma = 1/2 sum q (conic d)(conic d)^T, i.e. S3 = sum q u^2,
   // S4 = sum q u v, S5 = sum q v^2 are the covariance gradient up to the factors below -- K7 forms them per pixel
-  // (render.hip). The lineage goes through dL/dconic and divides by det^2 + 1e-7 instead of det^2: the factor
+  // (render_bwd.hip). The lineage goes through dL/dconic and divides by det^2 + 1e-7 instead of det^2: the factor
   // det^2 / (det^2 + 1e-7) keeps that regulariser (SEMANTICS.md section 5).
   gndx = S1 * (0.5f * (float)W);
   gndy = S2 * (0.5f * (float)H);
@@ -203,7 +204,7 @@ __device__ __forceinline__ void sigma_backward(const float dS[9], const float R[
 __device__ __forceinline__ float scale_draw(float act, float pre, bool noisy, float n) {
   return noisy ? (pre >= 0.0f ? act * (1.0f + n * (kSqrtPoint2 / 4.0f)) : 0.0f) : act;
 }
-// ---- K7's per-Gaussian sums: a row of 16 doubles, 12 used (render.hip, render_bwd_body) -- wave results added across
+// ---- K7's per-Gaussian sums: a row of 16 doubles, 12 used (render_bwd.hip, render_bwd_body) -- wave results added across
 // waves in double, rounded to fp32 HERE, once. partial_rows() hands them out as the chain rule below was written:
 // a = (S1, S2, S3, S4), b = (S5, dL/dopacity, r, g), c = (b, depth, b', depth').
 struct PartialRaw { float4 w[6]; };     // as loaded: 12 doubles, still raw bits (conversions wait for the loads: do them late)
@@ -266,7 +267,7 @@ k_preprocess_bwd(const GsrView v, const GsrGaussians g, const TAB sc, const GTAB
   if (vis) {
     px = p_xyz[3 * row]; py = p_xyz[3 * row + 1]; pz = p_xyz[3 * row + 2];
     partial_rows(partial_load(partials, i), pa, pb, pc);
-    pc.x += pc.z; pc.y += pc.w;      // (K7 commits the last two sums from the two halves of a wave: render.hip, reduce10)
+    pc.x += pc.z; pc.y += pc.w;      // (K7 commits the last two sums from the two halves of a wave: render_bwd.hip, reduce10)
   }
   const float S1 = pa.x, S2 = pa.y, S3 = pa.z, S4 = pa.w, S5 = pb.x, gop = pb.y;
   float gndx = 0.f, gndy = 0.f;
@@ -942,7 +943,7 @@ k_preprocess_bwd_views(const GsrView v, const GsrGaussians g, const K8Views vb, 
       } else {
         partial_rows(p_cur, pa, pb, pc);
       }
-      pc.x += pc.z; pc.y += pc.w;      // (K7 commits the last two sums from the two halves of a wave: render.hip, reduce10)
+      pc.x += pc.z; pc.y += pc.w;      // (K7 commits the last two sums from the two halves of a wave: render_bwd.hip, reduce10)
       if (vb.restore) partial_zero(vb.partials[vv], i);     // GsrGrads.scratch_clean: leave the scratch as it was found
       gop += pb.y;
       const float grgb[3] = {pb.z, pb.w, pc.x};

@@ -74,7 +74,7 @@ static int32_t imin(int32_t a, int32_t b) { return a < b ? a : b; }
 
 /* exp() of the compositing loops -- THE definition (SEMANTICS.md section 4): 2^(x log2 e) with a round-to-nearest
  * split t = n + f, f in [-1/2, 1/2], a degree-5 polynomial in Horner form and an exact scaling by 2^n. IEEE
- * operations only (one rounding per *, -, fmaf; rintf = round-half-even; ldexpf exact), so render.hip evaluates the
+ * operations only (one rounding per *, -, fmaf; rintf = round-half-even; ldexpf exact), so gsr_render.h evaluates the
  * very same expression tree (v_mul, v_rndne, v_sub, 5 x v_fma, v_cvt_i32, v_ldexp) and the two agree BIT FOR BIT --
  * which is what keeps the hard gates (alpha >= 1/255, T >= 1e-4) on the same side in both. Accuracy: <= 1.7e-7
  * relative from the polynomial + the rounding of t (<= 6e-8 |t|), the class of the lineage's __expf. exp(0) = 1. */

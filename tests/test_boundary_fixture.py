@@ -105,7 +105,7 @@ def test_hip_replays_the_record(built_lib, c_oracle, name):
     # With the upstream as recorded the disp normalisation puts |dL/d(depth, alpha)| = 7e4 on two pixels (<= 1 elsewhere).
     # Rounds 1-3 needed 3e-4 here: (i) the order of K7's fp32 atomics moved dL/dopacity between 1e-5 and 1e-4 from run to run --
     # the cross-wave sums are now added in double; (ii) s - R, the difference of two ~4e5 dot products that cancels in front of
-    # an opaque object, carried eps x 4e5 -- K7 now carries the behind-state relative to the segment's depth (render.hip,
+    # an opaque object, carried eps x 4e5 -- K7 now carries the behind-state relative to the segment's depth (render_bwd.hip,
     # render_bwd_body). What is left is fp32 per-pixel arithmetic on 7e4-weighted terms: measured <= 2.4e-5, bar 3e-5, and
     # the eight runs below give the same bits.
     for k, ref in c["grads"].items():

@@ -78,7 +78,7 @@ def run(cfg):
                 continue
             # the host picks the forward variant (list-parallel / whole-tile: GsrBinning.fwd_mode) per launch from the
             # previous launch's statistics -- a batch may take the other one than a single view, and the two differ in the
-            # association of the colour / depth sums (render.hip): ulps, not bits
+            # association of the colour / depth sums (render_fwd.hip): ulps, not bits
             VARIANT[0] += 1
             for what, a, b in (("image", img, rimg), ("depth_alpha", da, rda)):
                 e = float((a.detach().double() - b.detach().double()).abs().max())

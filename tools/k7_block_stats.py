@@ -3,7 +3,7 @@
 reduces + commits ONCE per (splat, tile) instead of once per (splat, block)). Computed on the CPU from the
 scalar C oracle's lists (oracle/gsr_oracle.c: point_list, ranges, n_contrib, the projected splat table) with the kernels' own
 gates at the pixel centres: block (tile, b) is HIT by list entry e when some pixel of the block has e < n_contrib (still alive),
-power <= 0 and alpha >= 1/255. Instruction model from render.hip's ISA (DESIGN.md "Issue costs"): per hit block ~65 VALU for the
+power <= 0 and alpha >= 1/255. Instruction model from render_bwd.hip's ISA (DESIGN.md "Issue costs"): per hit block ~65 VALU for the
 per-pixel work + 27 for reduce10 / convert / address / atomic today; whole-tile: 68 per hit block (3 more: accumulate instead of
 assign), 10 to clear the sums + 27 once per (splat, tile).   usage: python tools/k7_block_stats.py [P] [res] [--init-opacity] [--indoor]"""
 import os

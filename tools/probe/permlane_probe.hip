@@ -1,5 +1,5 @@
 // Prints the lane permutation of v_permlane32_swap / v_permlane16_swap on gfx950 (used to design the
-// transposed wave reduction in render.hip).
+// transposed wave reduction in render_bwd.hip).
 #include <hip/hip_runtime.h>
 #include <cstdio>
 __global__ void k(unsigned* out) {

@@ -1,5 +1,5 @@
 // VALU issue-rate probe for gfx950: how many shader cycles one SIMD spends per wave64 instruction, for the
-// instruction kinds the compositing kernels (render.hip) are made of, at 1 / 2 / 4 / 8 waves per SIMD.
+// instruction kinds the compositing kernels (render_fwd.hip, render_bwd.hip) are made of, at 1 / 2 / 4 / 8 waves per SIMD.
 // Answers the design question "does v_pk_fma_f32 (two pixels per lane) buy anything on this part?".
 //   build: hipcc --offload-arch=gfx950 -O2 -o valu_rate valu_rate.hip ; run on the GPU box: ./valu_rate
 #include <hip/hip_runtime.h>
