@@ -260,11 +260,11 @@ def pick_seg_len(cap, n_views: int = 1) -> int:
 
 def _forward_steps(s: GaussianRasterizationSettings, means3D, opacities, shs, colors_precomp, scales,
                    rotations, cov3D_precomp, want_keys, want_aux, mode, scene, batch, rc: RasterContext, seg_len=None):
-    """Generator behind rasterize_forward_raw. With batch = dict(scratch=<this view's slice of the batch's projection
-    scratch>, pinned=<pinned int64 [V]>, index=k, event=<Event>) it allocates and binds, YIELDS (view struct, geom struct)
-    for the caller to run gsr_forward_project_batch / gsr_forward_render_batch over all views, and continues when resumed.
-    Returns (outputs, state) through StopIteration.value."""
-    """Forward through the C ABI. Returns (outputs dict, _State). Used by the autograd Function and by tests.
+    """Forward through the C ABI, as the generator behind rasterize_forward_raw. Returns (outputs dict, _State) through
+    StopIteration.value. Used by the autograd Function and by tests.
+    With batch = dict(scratch=<this view's slice of the batch's projection scratch>, pinned=<pinned int64 [V]>, index=k,
+    event=<Event>) it allocates and binds, YIELDS (view struct, geom struct) for the caller to run
+    gsr_forward_project_batch / gsr_forward_render_batch over all views, and continues when resumed.
     scene (SURVEY.md 8f rank 2): {"models": [(xyz, scaling, rotation, opacity, features_dc, features_rest), ...] raw
     leaf tensors, "scale_noise": [P,3] | None, "sh_noise": [P,K,3] | None, "want_act": bool}; the per-Gaussian
     tensor arguments must then be None."""
@@ -694,47 +694,142 @@ def _bind_scratch(gr, sc: _Scratch, k: int = 0):
     gr.reach = sc.reach[k].data_ptr()
     gr.scratch_clean = 1
 
-def _backward_scene(st: _State, dL_dcolor, dL_ddepth_alpha, cam_grads: bool, model_grads, accumulate: bool,
-                    dL_dscales_out=None, stats=None, profile=None) -> dict:
-    """Backward of a scene forward: the parameter gradients are written (or, with accumulate, ADDED) straight into
-    per-model tensors shaped like the raw leaves. model_grads: list of 6-tuples (None entries are allocated here)."""
-    lib = L.load()
-    dev, P, K = st.dev, st.P, st.K
-    f32 = torch.float32
-    sc_struct, sc_keep = st.scene
-    sg = L.GsrSceneGrads()
-    outs = _model_grad_rows(sc_struct, sc_keep, model_grads, accumulate, K, dev)
-    for m, row in enumerate(outs):
+
+# ---- the backward's host driver: the pieces the four entry points below share ----------------------------------------------
+def _prep_image_grads(dL_dcolor, dL_ddepth_alpha, dev) -> tuple:
+    """One view's upstream gradients as K7 reads them (pixel by pixel: no 16-byte requirement)."""
+    return _prep(dL_dcolor, "dL_dcolor", dev, align=4), _prep(dL_ddepth_alpha, "dL_ddepth_alpha", dev, align=4)
+
+
+def _cam_grad_tensors(cam_grads: bool, dev) -> dict:
+    """dL_dview / dL_dproj / dL_dcampos (the library adds to them: zero-initialised here), None when nobody asked."""
+    def z(n):
+        return torch.zeros(n, dtype=torch.float32, device=dev) if cam_grads else None
+    return dict(dL_dview=z(16), dL_dproj=z(16), dL_dcampos=z(3))
+
+
+def _arena_views(arena, g, P: int, K: int, dev) -> dict:
+    """The regions of `arena` the summed gradients go to ({} without one), after checking that it fits the Gaussians `g`."""
+    if arena is None:
+        return {}
+    if arena.P != P or (g.shs and arena.K != K) or arena.flat.device != dev:
+        raise ValueError("GradArena does not match this view's (P, K, device)")
+    return arena.views
+
+
+_SUMMED_GRADS = ("dL_dmeans3D", "dL_dopacities", "dL_dshs", "dL_dcolors", "dL_dscales", "dL_drotations", "dL_dcov3D")
+
+
+def _summed_grads(g, P: int, K: int, av: dict, dev) -> dict:
+    """The parameter-gradient tensors of a backward over the Gaussians `g` (GsrGaussians), named like the GsrGrads fields they
+    are bound to: a region of the arena (`av`, _arena_views) where it has one, a fresh tensor otherwise, None for an input the
+    forward did not get. Keys: _SUMMED_GRADS."""
+    def new(*shape, name=None):
+        t = av.get(name)
+        return t if t is not None else torch.empty(shape, dtype=torch.float32, device=dev)
+    return dict(dL_dmeans3D=new(P, 3, name="means3D"), dL_dopacities=new(P, 1, name="opacities"),
+                dL_dshs=new(P, K, 3, name="shs") if g.shs else None, dL_dcolors=new(P, 3) if g.colors_precomp else None,
+                dL_dscales=new(P, 3, name="scales") if g.scales else None,
+                dL_drotations=new(P, 4, name="rotations") if g.rotations else None,
+                dL_dcov3D=new(P, 6) if g.cov3D_precomp else None)
+
+
+def _bind_model_grads(sg, rows, K: int) -> None:
+    """rows (_model_grad_rows) -> the per-model pointers of one view's GsrSceneGrads."""
+    for m, row in enumerate(rows):
         mg = sg.models[m]
         mg.xyz, mg.scaling, mg.rotation, mg.opacity = _ptr(row[0]), _ptr(row[1]), _ptr(row[2]), _ptr(row[3])
         mg.features_dc, mg.features_rest = _ptr(row[4]), (_ptr(row[5]) if K > 1 else None)
-    o = dict(dL_dmeans2D=torch.empty((P, 3), dtype=f32, device=dev), model_grads=outs,
-             dL_dview=torch.zeros(16, dtype=f32, device=dev) if cam_grads else None,
-             dL_dproj=torch.zeros(16, dtype=f32, device=dev) if cam_grads else None,
-             dL_dcampos=torch.zeros(3, dtype=f32, device=dev) if cam_grads else None)
+
+
+def _zero_outside(accumulate: bool, has_arena: bool, arena_ok: bool, has_mask: bool, capturing: bool,
+                  trust_zeros: Optional[bool] = None, reuse: bool = False, token=None, mask_owner=None,
+                  per_view_scales: bool = False, V: int = 1) -> tuple:
+    """(GsrGrads.zero_outside of a call, whether the call is being captured into somebody else's graph). A set bit says that the
+    rows outside the reached bitmap are known to be zero, so that K8 clears what the bitmap names and nothing else: bit 0 for the
+    summed gradients (the arena's regions, or a persistent dict's own tensors), bit 1 for the per-view rows (only a persistent
+    dict keeps those). Pure: what the caller knows goes in; no tensor and no arena is looked at. The defaults are the one-view
+    call (rasterize_backward_raw), which keeps no dict: bit 0 at most.
+      accumulate, has_arena  a call that ADDS to an arena sets nothing (without an arena there is nothing to add to)
+      arena_ok         with an arena: its answer for the regions this call writes (_arena_zero_outside) -- bit 0
+      has_mask         there is a bitmap at all (the arena's, or a persistent dict's own one); without one nothing is set
+      reuse, token, mask_owner   the dict KEEPS its rows -- bit 1, and without an arena bit 0 as well -- when it came back as
+                       `reuse` carrying the token of a persistent call and, with an arena, that token is the arena's _mask_owner:
+                       the ARENA's bitmap describes this dict's per-view rows only if this dict's call wrote it last
+      per_view_scales  ONE view (V == 1) with "per-view" scales that keeps nothing: the library sees an ordinary single view, for
+                       which dL_dscales is one of the summed outputs bit 0 speaks for -- but the buffer is this call's own fresh
+                       [1,P,3] tensor, not the arena's region: bit 0 is cleared (tools/fuzz_views.py, seeds 90 / 160)
+      trust_zeros      False: nothing is set, whatever is known. None: nothing is set while the stream is `capturing` -- what is
+                       known now need not hold when the graph replays -- and the call then counts as a foreign capture (the
+                       caller touch()es the arena behind it). True: the caller vouches (graph.py checks before every replay)."""
+    foreign_capture = bool(trust_zeros is None and capturing)
+    trusted = not foreign_capture if trust_zeros is None else bool(trust_zeros)
+    if (accumulate and has_arena) or not has_mask or not trusted:
+        return 0, foreign_capture
+    keeps = bool(reuse and token is not None and (not has_arena or mask_owner is token))
+    zo = (1 if (arena_ok if has_arena else keeps) else 0) | (2 if keeps else 0)
+    if per_view_scales and V == 1 and not keeps:
+        zo &= ~1
+    return zo, foreign_capture
+
+
+def _enqueue_backward(entry: str, states, grs, image_grads, scratch: _Scratch, arena=None, profile=None) -> None:
+    """Hands one backward to the library: `entry` is "gsr_backward" (ONE state, passed by reference) or "gsr_backward_views"
+    (arrays of len(states) entries). grs: the GsrGrads array [V] with the output pointers filled in; row k of `scratch` is
+    bound here, through the module's _bind_scratch as it is at call time. image_grads: per view the prepared (dL_dcolor,
+    dL_ddepth_alpha); this frame holds them -- and the ctypes arrays -- until the library has returned.
+    The scratch is this call's alone for the length of the enqueue (re-zeroed first if the previous one failed half-way); a call
+    that raises leaves it dirty and the arena, if there is one, untrusted (touch())."""
+    lib = L.load()
+    V = len(states)
+    dev = states[0].dev
+    igs = (L.GsrImageGrads * V)()
+    for k, (gc, gda) in enumerate(image_grads):
+        igs[k].dL_dcolor, igs[k].dL_ddepth_alpha = gc.data_ptr(), gda.data_ptr()
+        _bind_scratch(grs[k], scratch, k)
+    if entry == "gsr_backward":
+        st = states[0]
+        args = (C.byref(st.view), C.byref(st.gauss), C.byref(st.geom), C.byref(st.binning), C.byref(st.images), igs, grs)
+    else:
+        args = (V, (L.GsrView * V)(*[st.view for st in states]), (L.GsrGaussians * V)(*[st.gauss for st in states]),
+                (L.GsrGeom * V)(*[st.geom for st in states]), (L.GsrBinning * V)(*[st.binning for st in states]),
+                (L.GsrImages * V)(*[st.images for st in states]), igs, grs)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    prof = profile.handle if profile is not None else None
+    ok = False
+    scratch.begin()        # (a reused dict's scratch as well: same exclusivity, same re-zeroing after a failed call)
+    try:
+        with torch.cuda.device(dev):
+            L.check(getattr(lib, entry)(*args, stream, prof), entry)
+        ok = True
+    finally:
+        scratch.end(ok)
+        if not ok and arena is not None:
+            arena.touch()
+
+
+def _backward_scene(st: _State, image_grads, cam_grads: bool, model_grads, accumulate: bool, dL_dscales_out=None,
+                    stats=None, profile=None) -> dict:
+    """Backward of a scene forward: the parameter gradients are written (or, with accumulate, ADDED) straight into
+    per-model tensors shaped like the raw leaves. model_grads: list of 6-tuples (None entries are allocated here)."""
+    dev, P, K = st.dev, st.P, st.K
+    sc_struct, sc_keep = st.scene
+    sg = L.GsrSceneGrads()
+    outs = _model_grad_rows(sc_struct, sc_keep, model_grads, accumulate, K, dev)
+    _bind_model_grads(sg, outs, K)
+    o = dict(dL_dmeans2D=torch.empty((P, 3), dtype=torch.float32, device=dev), model_grads=outs,
+             **_cam_grad_tensors(cam_grads, dev))
     scratch = _scratch_acquire(dev, 1, P)
-    gr = L.GsrGrads()
+    grs = (L.GsrGrads * 1)()
+    gr = grs[0]
     gr.dL_dmeans2D = o["dL_dmeans2D"].data_ptr()
     gr.dL_dview, gr.dL_dproj, gr.dL_dcampos = _ptr(o["dL_dview"]), _ptr(o["dL_dproj"]), _ptr(o["dL_dcampos"])
-    _bind_scratch(gr, scratch)
     gr.accumulate = int(bool(accumulate))
     dL_dscales_out = _prep(dL_dscales_out, "dL_dscales_out", dev)
     sg.dL_dscales_out = _ptr(dL_dscales_out)
     _bind_stats(gr, stats, P, dev)
     gr.scene = C.pointer(sg)
-    ig = L.GsrImageGrads()
-    ig.dL_dcolor, ig.dL_ddepth_alpha = dL_dcolor.data_ptr(), dL_ddepth_alpha.data_ptr()
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    prof = profile.handle if profile is not None else None
-    ok = False
-    scratch.begin()
-    try:
-        with torch.cuda.device(dev):
-            L.check(lib.gsr_backward(C.byref(st.view), C.byref(st.gauss), C.byref(st.geom), C.byref(st.binning),
-                                     C.byref(st.images), C.byref(ig), C.byref(gr), stream, prof), "gsr_backward")
-        ok = True
-    finally:
-        scratch.end(ok)
+    _enqueue_backward("gsr_backward", [st], grs, [image_grads], scratch, None, profile)
     return o
 
 
@@ -779,65 +874,35 @@ def _arena_written(arena, accumulate: bool, token=None, regions=None) -> None:
 def rasterize_backward_raw(st: _State, dL_dcolor, dL_ddepth_alpha, cam_grads: bool = False, arena=None,
                            accumulate: bool = False, model_grads=None, dL_dscales_out=None, stats=None,
                            profile=None) -> dict:
-    lib = L.load()
     dev, P, K = st.dev, st.P, st.K
     _check_versions(st)
-    dL_dcolor = _prep(dL_dcolor, "dL_dcolor", dev, align=4)           # (read pixel by pixel: no 16-byte requirement)
-    dL_ddepth_alpha = _prep(dL_ddepth_alpha, "dL_ddepth_alpha", dev, align=4)
+    image_grads = _prep_image_grads(dL_dcolor, dL_ddepth_alpha, dev)
     if st.scene is not None:
-        return _backward_scene(st, dL_dcolor, dL_ddepth_alpha, cam_grads, model_grads, accumulate, dL_dscales_out,
-                               stats, profile)
+        return _backward_scene(st, image_grads, cam_grads, model_grads, accumulate, dL_dscales_out, stats, profile)
     g = st.gauss
-    f32 = torch.float32
-    av = {}
-    if arena is not None:
-        if arena.P != P or (g.shs and arena.K != K) or arena.flat.device != dev:
-            raise ValueError("GradArena does not match this view's (P, K, device)")
-        av = arena.views
-
-    def new(*shape, name=None):
-        t = av.get(name)
-        return t if t is not None else torch.empty(shape, dtype=f32, device=dev)
-    o = dict(dL_dmeans3D=new(P, 3, name="means3D"), dL_dmeans2D=new(P, 3), dL_dopacities=new(P, 1, name="opacities"),
-             dL_dshs=new(P, K, 3, name="shs") if g.shs else None, dL_dcolors=new(P, 3) if g.colors_precomp else None,
-             dL_dscales=new(P, 3, name="scales") if g.scales else None,
-             dL_drotations=new(P, 4, name="rotations") if g.rotations else None,
-             dL_dcov3D=new(P, 6) if g.cov3D_precomp else None,
-             dL_dview=torch.zeros(16, dtype=f32, device=dev) if cam_grads else None,
-             dL_dproj=torch.zeros(16, dtype=f32, device=dev) if cam_grads else None,
-             dL_dcampos=torch.zeros(3, dtype=f32, device=dev) if cam_grads else None)
+    o = _summed_grads(g, P, K, _arena_views(arena, g, P, K, dev), dev)
+    o["dL_dmeans2D"] = torch.empty((P, 3), dtype=torch.float32, device=dev)
+    o.update(_cam_grad_tensors(cam_grads, dev))
     scratch = _scratch_acquire(dev, 1, P)
-    gr = L.GsrGrads()
+    grs = (L.GsrGrads * 1)()
+    gr = grs[0]
     for k, t in o.items():
         setattr(gr, k, _ptr(t))
-    _bind_scratch(gr, scratch)
-    gr.accumulate = int(bool(accumulate and arena is not None))
-    capturing = False
+    acc = bool(accumulate and arena is not None)
+    gr.accumulate = int(acc)
+    regions = _arena_regions(g)
+    foreign_capture = False
     if arena is not None and getattr(arena, "reached", None) is not None:
         gr.reached_mask = arena.reached.data_ptr()      # K8 marks the rows an exchange has to move (GradArena.reached_rows)
-        # (not under a capture: what is known now need not hold when the graph replays)
-        capturing = torch.cuda.is_current_stream_capturing()
-        gr.zero_outside = 0 if capturing else _arena_zero_outside(arena, gr.accumulate != 0, _arena_regions(g))
+        # (one view overwrites no per-view rows anybody keeps: bit 0 only, and nothing under a capture)
+        gr.zero_outside, foreign_capture = _zero_outside(acc, True, _arena_zero_outside(arena, acc, regions), True,
+                                                         torch.cuda.is_current_stream_capturing())
     _bind_stats(gr, stats, P, dev)
-    ig = L.GsrImageGrads()
-    ig.dL_dcolor, ig.dL_ddepth_alpha = dL_dcolor.data_ptr(), dL_ddepth_alpha.data_ptr()
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    prof = profile.handle if profile is not None else None
-    ok = False
-    scratch.begin()
-    try:
-        with torch.cuda.device(dev):
-            L.check(lib.gsr_backward(C.byref(st.view), C.byref(g), C.byref(st.geom), C.byref(st.binning),
-                                     C.byref(st.images), C.byref(ig), C.byref(gr), stream, prof), "gsr_backward")
-        ok = True
-    finally:
-        scratch.end(ok)
-        if not ok and arena is not None:
-            arena.touch()
-    if capturing and arena is not None:
+    _enqueue_backward("gsr_backward", [st], grs, [image_grads], scratch, arena, profile)
+    if foreign_capture:
         arena.touch()          # (nothing ran yet; the graph's replays are the capturer's business: nothing is known about the arena)
     else:
-        _arena_written(arena, gr.accumulate != 0, None, _arena_regions(g))
+        _arena_written(arena, acc, None, regions)
     return o
 
 
@@ -847,53 +912,30 @@ def rasterize_backward_views_scene_raw(states, dL_dcolors, dL_ddepth_alphas, mod
     K7 per view, one K8 pass over all views; the gradients of the raw leaves are the sums over the views, written to (or,
     with accumulate, added to) one tensor per leaf. dL_dscales_outs: per view, the gradient arriving through the returned
     scales (or None). stats / stats_views: see RasterContext."""
-    lib = L.load()
     V = len(states)
     st0 = states[0]
     dev, P, K = st0.dev, st0.P, st0.K
-    f32 = torch.float32
     for st in states:
         _check_versions(st)
     sc0, keep0 = st0.scene
     outs = _model_grad_rows(sc0, keep0, model_grads, accumulate, K, dev)
-    m2d = torch.empty((V, max(P, 1), 3), dtype=f32, device=dev)
+    m2d = torch.empty((V, max(P, 1), 3), dtype=torch.float32, device=dev)
     scratch = _scratch_acquire(dev, V, P)
-    views = (L.GsrView * V)(*[st.view for st in states])
-    gauss = (L.GsrGaussians * V)(*[st.gauss for st in states])
-    geoms = (L.GsrGeom * V)(*[st.geom for st in states])
-    bins = (L.GsrBinning * V)(*[st.binning for st in states])
-    imgs = (L.GsrImages * V)(*[st.images for st in states])
-    igs = (L.GsrImageGrads * V)()
+    image_grads = [_prep_image_grads(dL_dcolors[k], dL_ddepth_alphas[k], dev) for k in range(V)]
     grs = (L.GsrGrads * V)()
-    sgs = [L.GsrSceneGrads() for _ in range(V)]
+    sgs = [L.GsrSceneGrads() for _ in range(V)]     # (one per view: each carries its own dL_dscales_out)
     keep = []
-    counted = _stat_views(V, stats, stats_views)
     for k in range(V):
-        gc, gda = _prep(dL_dcolors[k], "dL_dcolor", dev, align=4), _prep(dL_ddepth_alphas[k], "dL_ddepth_alpha", dev, align=4)
         gso = _prep(dL_dscales_outs[k], "dL_dscales_out", dev) if dL_dscales_outs is not None else None
-        keep += [gc, gda, gso]
-        igs[k].dL_dcolor, igs[k].dL_ddepth_alpha = gc.data_ptr(), gda.data_ptr()
-        for m, row in enumerate(outs):
-            mg = sgs[k].models[m]
-            mg.xyz, mg.scaling, mg.rotation, mg.opacity = _ptr(row[0]), _ptr(row[1]), _ptr(row[2]), _ptr(row[3])
-            mg.features_dc, mg.features_rest = _ptr(row[4]), (_ptr(row[5]) if K > 1 else None)
+        keep.append(gso)
+        _bind_model_grads(sgs[k], outs, K)
         sgs[k].dL_dscales_out = _ptr(gso)
         grs[k].scene = C.pointer(sgs[k])
         grs[k].dL_dmeans2D = m2d[k].data_ptr()
-        _bind_scratch(grs[k], scratch, k)
         grs[k].accumulate = int(bool(accumulate))
-        if k in counted:
-            _bind_stats(grs[k], stats, P, dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    prof = profile.handle if profile is not None else None
-    ok = False
-    scratch.begin()
-    try:
-        with torch.cuda.device(dev):
-            L.check(lib.gsr_backward_views(V, views, gauss, geoms, bins, imgs, igs, grs, stream, prof), "gsr_backward_views")
-        ok = True
-    finally:
-        scratch.end(ok)
+    for k in _stat_views(V, stats, stats_views):
+        _bind_stats(grs[k], stats, P, dev)
+    _enqueue_backward("gsr_backward_views", states, grs, image_grads, scratch, None, profile)
     return dict(dL_dmeans2D=m2d[:, :P], model_grads=outs)
 
 
@@ -912,109 +954,56 @@ def rasterize_backward_views_raw(states, dL_dcolors, dL_ddepth_alphas, arena=Non
     everything nothing reached (118 + 24 MB of zeros per 4-view step at C3). trust_zeros=False: never (the call clears every row
     nothing reached, whatever is known about the tensors); None (default): unless the stream is being captured -- what is known now
     need not hold when somebody else's graph replays (graph.py, which checks before every replay, says True explicitly)."""
-    lib = L.load()
     V = len(states)
     st0 = states[0]
     dev, P, K = st0.dev, st0.P, st0.K
     g = st0.gauss
-    f32 = torch.float32
     for st in states:
         _check_versions(st)
-    av = {}
-    if arena is not None:
-        if arena.P != P or (g.shs and arena.K != K) or arena.flat.device != dev:
-            raise ValueError("GradArena does not match this view's (P, K, device)")
-        av = arena.views
-
-    def new(*shape, name=None):
-        t = av.get(name)
-        return t if t is not None else torch.empty(shape, dtype=f32, device=dev)
-    names = ("dL_dmeans3D", "dL_dopacities", "dL_dshs", "dL_dcolors", "dL_dscales", "dL_drotations", "dL_dcov3D")
+    av = _arena_views(arena, g, P, K, dev)
     if per_view_scales is None:
         per_view_scales = any(st.gauss.scales != g.scales for st in states)
     own_mask = None
     if reuse is not None:
-        o = {k: reuse[k] for k in names}
+        o = {k: reuse[k] for k in _SUMMED_GRADS}
         m2d, scratch = reuse["_m2d"], reuse["_scratch"]
         own_mask = reuse.get("_reached")
     else:
-        o = dict(dL_dmeans3D=new(P, 3, name="means3D"), dL_dopacities=new(P, 1, name="opacities"),
-                 dL_dshs=new(P, K, 3, name="shs") if g.shs else None, dL_dcolors=new(P, 3) if g.colors_precomp else None,
-                 dL_dscales=new(P, 3, name="scales") if g.scales else None,
-                 dL_drotations=new(P, 4, name="rotations") if g.rotations else None,
-                 dL_dcov3D=new(P, 6) if g.cov3D_precomp else None)
+        o = _summed_grads(g, P, K, av, dev)
         if per_view_scales:        # every view has its own scales tensor -> its own scale gradient
-            o["dL_dscales"] = torch.empty((V, P, 3), dtype=f32, device=dev)
-        m2d = torch.empty((V, max(P, 1), 3), dtype=f32, device=dev)
+            o["dL_dscales"] = torch.empty((V, P, 3), dtype=torch.float32, device=dev)
+        m2d = torch.empty((V, max(P, 1), 3), dtype=torch.float32, device=dev)
         # (a reused dict -- graph capture -- keeps the scratch of the call that made it: static addresses, and the
         #  captured K7 / K8 pair maintains the all-zero invariant like an eager one; private_scratch: that call asks for a
         #  scratch of its own instead of the cached one eager calls share)
         scratch = _scratch_acquire(dev, V, P, private=private_scratch)
         if persistent and arena is None:
             own_mask = torch.zeros((P + 63) // 64, dtype=torch.int64, device=dev)
-    # GsrGrads.zero_outside: bit 0 the summed gradients (the arena, or a persistent dict's own tensors), bit 1 the per-view rows
-    # (only a persistent dict keeps those)
     acc = bool(accumulate and arena is not None)
     token = reuse.get("_token") if reuse is not None else (object() if persistent else None)
-    has_mask = (arena is not None and getattr(arena, "reached", None) is not None) or own_mask is not None
-    # (with an arena the bitmap is the ARENA's: it describes this dict's per-view rows only if this dict's call wrote it last)
-    keeps = reuse is not None and token is not None and not acc and has_mask and \
-        (arena is None or getattr(arena, "_mask_owner", None) is token)
+    mask = getattr(arena, "reached", None) if arena is not None else None       # the bitmap K8 marks: the arena's ...
+    if mask is None:
+        mask = own_mask                                                         # ... or a persistent dict's own
     regions = _arena_regions(g, per_view_scales)
-    zo = (_arena_zero_outside(arena, acc, regions) if arena is not None else (1 if keeps else 0)) | (2 if keeps else 0)
-    if per_view_scales and V == 1 and not keeps:
-        # ONE view with "per-view" scales: the library sees an ordinary single view, for which dL_dscales is one of the summed
-        # outputs bit 0 speaks for -- but the buffer is this call's own fresh [1,P,3] tensor, not the arena's region (found by
-        # tools/fuzz_views.py, seeds 90 / 160: uninitialised rows in dL/dscales)
-        zo &= ~1
-    foreign_capture = trust_zeros is None and torch.cuda.is_current_stream_capturing()
-    if trust_zeros is None:
-        trust_zeros = not foreign_capture
-    if not trust_zeros:
-        zo = 0
-    views = (L.GsrView * V)(*[st.view for st in states])
-    gauss = (L.GsrGaussians * V)(*[st.gauss for st in states])
-    geoms = (L.GsrGeom * V)(*[st.geom for st in states])
-    bins = (L.GsrBinning * V)(*[st.binning for st in states])
-    imgs = (L.GsrImages * V)(*[st.images for st in states])
-    igs = (L.GsrImageGrads * V)()
+    zo, foreign_capture = _zero_outside(acc, arena is not None, _arena_zero_outside(arena, acc, regions), mask is not None,
+                                        torch.cuda.is_current_stream_capturing(), trust_zeros, reuse is not None, token,
+                                        getattr(arena, "_mask_owner", None), per_view_scales, V)
+    image_grads = [_prep_image_grads(dL_dcolors[k], dL_ddepth_alphas[k], dev) for k in range(V)]
     grs = (L.GsrGrads * V)()
-    keep = []
-    counted = _stat_views(V, stats, stats_views)
     for k in range(V):
-        gc, gda = _prep(dL_dcolors[k], "dL_dcolor", dev, align=4), _prep(dL_ddepth_alphas[k], "dL_ddepth_alpha", dev, align=4)
-        keep += [gc, gda]
-        igs[k].dL_dcolor, igs[k].dL_ddepth_alpha = gc.data_ptr(), gda.data_ptr()
+        gr = grs[k]
         for name, t in o.items():
-            if name.startswith("_"):
-                continue
-            setattr(grs[k], name, _ptr(t))
+            setattr(gr, name, _ptr(t))
         if per_view_scales:
-            grs[k].dL_dscales = o["dL_dscales"][k].data_ptr()
-        grs[k].dL_dmeans2D = m2d[k].data_ptr()
-        _bind_scratch(grs[k], scratch, k)
-        grs[k].accumulate = int(acc)
-        if arena is not None and getattr(arena, "reached", None) is not None:
-            grs[k].reached_mask = arena.reached.data_ptr()
-            grs[k].zero_outside = zo
-        elif own_mask is not None:
-            grs[k].reached_mask = own_mask.data_ptr()
-            grs[k].zero_outside = zo
-        if k in counted:
-            _bind_stats(grs[k], stats, P, dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    prof = profile.handle if profile is not None else None
-    ok = False
-    scratch.begin()        # (a reused dict's scratch as well: same exclusivity, same re-zeroing after a failed call)
-    try:
-        with torch.cuda.device(dev):
-            L.check(lib.gsr_backward_views(V, views, gauss, geoms, bins, imgs, igs, grs, stream, prof),
-                    "gsr_backward_views")
-        ok = True
-    finally:
-        scratch.end(ok)
-        if not ok and arena is not None:
-            arena.touch()
+            gr.dL_dscales = o["dL_dscales"][k].data_ptr()
+        gr.dL_dmeans2D = m2d[k].data_ptr()
+        gr.accumulate = int(acc)
+        if mask is not None:
+            gr.reached_mask = mask.data_ptr()
+            gr.zero_outside = zo
+    for k in _stat_views(V, stats, stats_views):
+        _bind_stats(grs[k], stats, P, dev)
+    _enqueue_backward("gsr_backward_views", states, grs, image_grads, scratch, arena, profile)
     if foreign_capture and arena is not None:
         arena.touch()          # (nothing ran; when and how often the graph will run is the capturer's business: nothing is known)
     else:

@@ -359,3 +359,111 @@ def test_arena_rebuilds_its_bitmap_from_its_contents():
     a.flat.zero_()
     a.rebuild_reached()
     assert a.reached_rows().numel() == 0 and int(a.reached.abs().sum()) == 0
+
+
+def test_zero_outside_decision_table():
+    """rasterizer._zero_outside: which GsrGrads.zero_outside bits a backward may set -- bit 0 the summed gradients, bit 1 the
+    per-view rows -- and whether the call is a foreign capture. The expectations are the rules of its docstring written out;
+    every past defect here was a wrong entry of this table (one view with per-view scales: fuzz seeds 90 / 160; the foreign
+    capture; the arena some other call wrote last)."""
+    from dreamscene_amd import rasterizer as R
+    mine, other = object(), object()
+    # a 4-view call into an arena whose regions are known to be zero outside its bitmap, nothing being captured
+    arena = dict(accumulate=False, has_arena=True, arena_ok=True, has_mask=True, capturing=False, trust_zeros=None,
+                 reuse=False, token=None, mask_owner=None, per_view_scales=False, V=4)
+    # a persistent dict without an arena: a bitmap of its own, a token from its first call
+    own = dict(arena, has_arena=False, arena_ok=False, token=mine)
+    table = [
+        ("arena, first call: the summed gradients only", arena, (1, False)),
+        ("arena, first call of a persistent dict: its rows are fresh", dict(arena, token=mine), (1, False)),
+        ("arena that cannot vouch for the regions", dict(arena, arena_ok=False), (0, False)),
+        ("arena, reuse by the dict that wrote the bitmap last", dict(arena, reuse=True, token=mine, mask_owner=mine), (3, False)),
+        ("... bit 0 stays the arena's answer", dict(arena, arena_ok=False, reuse=True, token=mine, mask_owner=mine), (2, False)),
+        ("arena whose bitmap another dict wrote last: never bit 1", dict(arena, reuse=True, token=mine, mask_owner=other), (1, False)),
+        ("... nor when nobody owns it", dict(arena, reuse=True, token=mine, mask_owner=None), (1, False)),
+        ("... nor with a dict that never was persistent", dict(arena, reuse=True, token=None, mask_owner=None), (1, False)),
+        ("accumulate into an arena", dict(arena, accumulate=True), (0, False)),
+        ("accumulate, even for the owner of the bitmap", dict(arena, accumulate=True, reuse=True, token=mine, mask_owner=mine), (0, False)),
+        ("persistent dict without an arena, first call", own, (0, False)),
+        ("persistent dict without an arena, reuse", dict(own, reuse=True), (3, False)),
+        ("... `accumulate` without an arena adds to nothing", dict(own, reuse=True, accumulate=True), (3, False)),
+        ("no bitmap at all: no arena, not persistent", dict(own, has_mask=False, token=None), (0, False)),
+        ("no bitmap at all, whatever else holds", dict(own, has_mask=False, reuse=True), (0, False)),
+        ("an arena without a bitmap", dict(arena, has_mask=False, reuse=True, token=mine, mask_owner=mine), (0, False)),
+        ("ONE view with per-view scales into an arena (fuzz seeds 90 / 160)", dict(arena, per_view_scales=True, V=1), (0, False)),
+        ("... two such views: dL_dscales is no summed output", dict(arena, per_view_scales=True, V=2), (1, False)),
+        ("... one such view of a dict that keeps its rows", dict(arena, per_view_scales=True, V=1, reuse=True, token=mine, mask_owner=mine), (3, False)),
+        ("... and of one that does not own the arena's bitmap", dict(arena, per_view_scales=True, V=1, reuse=True, token=mine, mask_owner=other), (0, False)),
+        ("trust_zeros=False", dict(arena, trust_zeros=False, reuse=True, token=mine, mask_owner=mine), (0, False)),
+        ("trust_zeros=False under a capture is no foreign capture", dict(arena, trust_zeros=False, capturing=True), (0, False)),
+        ("trust_zeros=None on a capturing stream", dict(arena, reuse=True, token=mine, mask_owner=mine, capturing=True), (0, True)),
+        ("... without an arena as well", dict(own, reuse=True, capturing=True), (0, True)),
+        ("trust_zeros=True on a capturing stream: the caller vouches", dict(arena, trust_zeros=True, reuse=True, token=mine, mask_owner=mine, capturing=True), (3, False)),
+        ("trust_zeros=True vouches for nothing the call does not know", dict(arena, trust_zeros=True, arena_ok=False), (0, False)),
+    ]
+    for what, kw, want in table:
+        assert R._zero_outside(**kw) == want, what
+    # the one-view call (rasterize_backward_raw) is the defaults: bit 0 only, and nothing while capturing
+    assert R._zero_outside(False, True, True, True, False) == (1, False)
+    assert R._zero_outside(False, True, False, True, False) == (0, False)
+    assert R._zero_outside(True, True, True, True, False) == (0, False)
+    assert R._zero_outside(False, True, True, True, True) == (0, True)
+
+
+def test_stat_views_picks_the_counted_views():
+    """rasterizer._stat_views: no statistics tensors -> no view counts; by default the LAST view (what the reference's trainers
+    use); "all"; indices wrap modulo V like Python's negative indices do."""
+    from dreamscene_amd import rasterizer as R
+    stats = (torch.zeros(5), torch.zeros(5), torch.zeros(5))
+    assert R._stat_views(3, None, None) == set() and R._stat_views(3, None, "all") == set() and R._stat_views(3, None, [0]) == set()
+    assert R._stat_views(3, stats, None) == {2} and R._stat_views(1, stats, None) == {0}
+    assert R._stat_views(3, stats, "all") == {0, 1, 2}
+    assert R._stat_views(3, stats, [0]) == {0} and R._stat_views(3, stats, (1, 1, 2)) == {1, 2}
+    assert R._stat_views(3, stats, [-1]) == {2} and R._stat_views(3, stats, [-3, 4]) == {0, 1} and R._stat_views(3, stats, [3]) == {0}
+    assert R._stat_views(3, stats, []) == set()
+    with pytest.raises(ValueError, match="stats_views is None"):
+        R._stat_views(3, stats, "last")
+
+
+def test_backward_validates_gradient_and_statistics_tensors():
+    """rasterizer._model_grad_rows / _bind_stats hand raw pointers to K8: a tensor of the wrong shape, stride or size must be
+    refused on the host (CPU tensors: nothing here touches a device)."""
+    from dreamscene_amd import _lib as L, rasterizer as R
+    cpu = torch.device("cpu")
+    n, K = 5, 4
+    leaves = (torch.zeros(n, 3), torch.zeros(n, 3), torch.zeros(n, 4), torch.zeros(n, 1), torch.zeros(n, 1, 3),
+              torch.zeros(n, K - 1, 3))
+    sc = L.GsrScene()
+    sc.n_models = 1
+    given = tuple(torch.ones_like(t) for t in leaves)
+    rows = R._model_grad_rows(sc, [leaves], [given], True, K, cpu)
+    assert len(rows) == 1 and all(a is b for a, b in zip(rows[0], given))          # the caller's own tensors, not copies
+    rows = R._model_grad_rows(sc, [leaves], None, False, K, cpu)                    # nothing given: allocated like the leaves
+    assert [tuple(t.shape) for t in rows[0]] == [tuple(t.shape) for t in leaves]
+    # an absent leaf has no gradient; an empty one (a model of K = 1 has no features_rest) gets an empty one
+    rows = R._model_grad_rows(sc, [leaves[:5] + (None,)], None, False, K, cpu)
+    assert rows[0][5] is None
+    rows = R._model_grad_rows(sc, [leaves[:5] + (torch.zeros(n, 0, 3),)], [given[:5] + (None,)], True, K, cpu)
+    assert rows[0][5].shape == (n, 0, 3)
+    with pytest.raises(ValueError, match="accumulate=True needs the gradient tensors"):
+        R._model_grad_rows(sc, [leaves], None, True, K, cpu)
+    with pytest.raises(ValueError, match="accumulate=True needs the gradient tensors"):
+        R._model_grad_rows(sc, [leaves], [given[:2] + (None,) + given[3:]], True, K, cpu)
+    bad = "model gradient tensors must match the raw leaves"
+    with pytest.raises(ValueError, match=bad):                                      # wrong shape
+        R._model_grad_rows(sc, [leaves], [(torch.zeros(n + 1, 3),) + given[1:]], False, K, cpu)
+    with pytest.raises(ValueError, match=bad):                                      # right shape, not contiguous
+        R._model_grad_rows(sc, [leaves], [(torch.zeros(3, n).t(),) + given[1:]], False, K, cpu)
+    with pytest.raises(ValueError, match=bad):                                      # not fp32
+        R._model_grad_rows(sc, [leaves], [(torch.zeros(n, 3, dtype=torch.float64),) + given[1:]], False, K, cpu)
+
+    stats = (torch.zeros(n), torch.zeros(n), torch.zeros(n))
+    gr = L.GsrGrads()
+    R._bind_stats(gr, None, n, cpu)
+    assert not gr.stat_max_radii2D and not gr.stat_xyz_gradient_accum and not gr.stat_denom
+    R._bind_stats(gr, stats, n, cpu)
+    assert (gr.stat_max_radii2D, gr.stat_xyz_gradient_accum, gr.stat_denom) == tuple(t.data_ptr() for t in stats)
+    bad = "densify_stats tensors must be contiguous fp32 with P elements"
+    for wrong in (torch.zeros(n + 1), torch.zeros(2 * n)[::2], torch.zeros(n, dtype=torch.float64)):
+        with pytest.raises(ValueError, match=bad):
+            R._bind_stats(L.GsrGrads(), (stats[0], wrong, stats[2]), n, cpu)

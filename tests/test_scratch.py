@@ -154,41 +154,60 @@ def test_scene_forms_clear_the_scratch_behind_them(built_lib):
                 assert float(np.abs(a - b).max()) <= 1e-5 * rel_scale(b)
 
 
-def test_a_failed_enqueue_releases_the_scratch_and_the_next_call_rezeroes_it(built_lib, monkeypatch):
+@pytest.mark.parametrize("door", ["raw", "raw_scene", "views", "views_scene"])
+def test_a_failed_enqueue_releases_the_scratch_and_the_next_call_rezeroes_it(built_lib, monkeypatch, door):
     """the persistent K7 -> K8 scratch is locked for the length of one enqueue (two host threads on a stream must
     not interleave K7(A), K7(B), K8(A)); a call that raises half-way releases the lock, leaves the scratch flagged dirty, and
-    the next call zeroes it before use."""
-    from dreamscene_amd import rasterizer as R, synth, _lib as L
+    the next call zeroes it before use. For every entry point of the backward: rasterize_backward_raw on a plain and on a scene
+    state, the two views functions (two views). The two that take a GradArena write into one, which must not trust its
+    reached-row bitmap after the failure."""
+    from dreamscene_amd import multiview, rasterizer as R, _lib as L
+    from tests.test_backward_doors import P, forward, gaussians, raw_model, views_setup
     dev = torch.device(DEV)
-    P, H, W, K, D = 1500, 96, 96, 16, 3
-    g, _ = small_scene(P=P, H=H, W=W, K=K, seed=17)
-    cam = synth.object_cameras(2, H, W, radius=3.0)[1]
-    t = {k: torch.tensor(v, device=dev) for k, v in g.items()}
-    s = settings_for(cam, [1, 1, 1], D, dev)
-    gi, gda = (torch.tensor(x, device=dev) for x in synth.upstream_grads(H, W, 0))
+    K, D = 16, 3
+    scene, V = door.endswith("scene"), (2 if door.startswith("views") else 1)
+    t = gaussians(K, seed=17)
+    model = raw_model(t) if scene else None
+    sets, gis, gdas = views_setup(D, V)
+    arena = None if scene else multiview.GradArena(P, K, dev)
 
     def backward():
-        out, st = R.rasterize_forward_raw(s, t["means3D"], t["opacities"], t["shs"], None, t["scales"], t["rotations"], None)
-        return R.rasterize_backward_raw(st, gi, gda)
+        sts = [forward(R, s, t, model)[1] for s in sets]
+        if door == "views":
+            o = R.rasterize_backward_views_raw(sts, gis, gdas, arena=arena)
+        elif door == "views_scene":
+            o = R.rasterize_backward_views_scene_raw(sts, gis, gdas)
+        else:
+            o = R.rasterize_backward_raw(sts[0], gis[0], gdas[0], arena=arena)
+        torch.cuda.synchronize()
+        res = {f"leaf {j}": x for j, x in enumerate(o["model_grads"][0])} if scene else \
+            {k: o[k] for k in ("dL_dmeans3D", "dL_dshs", "dL_dscales", "dL_drotations", "dL_dopacities")}
+        res["dL_dmeans2D"] = o["dL_dmeans2D"]
+        return {k: x.clone() for k, x in res.items()}       # (with an arena every call returns the same memory)
     ref = backward()
-    torch.cuda.synchronize()
+    assert sum(float(x.abs().sum()) for x in ref.values()) > 0
     sc = list(R._SCRATCH.values())[-1]              # (most recently used: this call's)
-    assert sc.partials.shape[:2] == (1, P)
+    assert sc.partials.shape[:2] == (V, P)
+    assert arena is None or arena.reached_valid
     real_check = L.check
+    failed = []
 
     def failing_check(code, what):
-        if what == "gsr_backward":
+        if what == ("gsr_backward_views" if V > 1 else "gsr_backward"):
             sc.partials.fill_(3.0)              # (what a half-enqueued K7 would leave behind)
+            failed.append(what)
             raise L.GsrError("injected failure")
         return real_check(code, what)
     monkeypatch.setattr(R.L, "check", failing_check)
     with pytest.raises(L.GsrError):
         backward()
     monkeypatch.setattr(R.L, "check", real_check)
+    assert len(failed) == 1
     assert sc.dirty and not sc.lock.locked()
+    assert arena is None or not arena.reached_valid
     again = backward()
-    torch.cuda.synchronize()
     assert not sc.dirty and not sc.lock.locked()
-    for k in ("dL_dmeans3D", "dL_dshs", "dL_dscales", "dL_drotations", "dL_dopacities"):
+    assert arena is None or arena.reached_valid
+    for k in ref:
         same_bits(ref[k], again[k], k)
     assert int(torch.count_nonzero(sc.partials)) == 0
