@@ -148,6 +148,22 @@ class GsrFrameViews(C.Structure):
                 ("image", _f * GSR_MAX_FRAME_VIEWS), ("depth_alpha", _f * GSR_MAX_FRAME_VIEWS)]
 
 
+GSR_MAX_PHOTO_VIEWS = 16
+GSR_MAX_PHOTO_CHANNELS = 4
+GSR_PHOTO_WINDOW = 11
+
+
+class GsrPhotoViews(C.Structure):
+    _fields_ = [("n_views", C.c_int32), ("channels", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("target_is_half", C.c_int32), ("round_image_to_half", C.c_int32),
+                ("image", _f * GSR_MAX_PHOTO_VIEWS), ("target", _f * GSR_MAX_PHOTO_VIEWS),
+                ("dL_dimage", _f * GSR_MAX_PHOTO_VIEWS)]
+
+
+class GsrPhotoWeights(C.Structure):
+    _fields_ = [("l2", C.c_float), ("l1", C.c_float), ("dssim", C.c_float)]
+
+
 # every symbol include/gsrast.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("gsr_adam_step", C.c_int, [C.POINTER(GsrAdamGroup), C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,
@@ -213,6 +229,11 @@ SYMBOLS = [
     ("gsr_place", C.c_int, [C.POINTER(GsrPlacement), C.c_void_p, C.c_size_t, C.c_void_p]),
     ("gsr_frames_scratch_bytes", C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     ("gsr_frames_quantize", C.c_int, [C.POINTER(GsrFrameViews), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("gsr_photo_window", None, [C.POINTER(C.c_float)]),
+    ("gsr_photo_scratch_bytes", C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    ("gsr_photo_forward", C.c_int, [C.POINTER(GsrPhotoViews), C.POINTER(GsrPhotoWeights), C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("gsr_photo_backward", C.c_int, [C.POINTER(GsrPhotoViews), C.POINTER(GsrPhotoWeights), C.c_void_p, C.c_void_p, C.c_void_p]),
     ("gsr_backward", C.c_int, [C.POINTER(GsrView), C.POINTER(GsrGaussians), C.POINTER(GsrGeom), C.POINTER(GsrBinning),
                                C.POINTER(GsrImages), C.POINTER(GsrImageGrads), C.POINTER(GsrGrads), C.c_void_p,
                                C.c_void_p]),

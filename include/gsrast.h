@@ -634,6 +634,54 @@ size_t gsr_frames_scratch_bytes(int32_t n_views, int32_t height, int32_t width);
 int gsr_frames_quantize(const GsrFrameViews* views, uint8_t* rgb, uint8_t* depth, void* scratch, size_t scratch_bytes,
                         void* stream);
 
+/* ---- photometric loss: l2_loss, l1_loss and ssim of the reconstructive refine steps (utils/system_utils.py:59-126; training/
+ * object_trainer.py:626-653, training/scene_trainer.py:1269-1293, :1737-1770; dreamscene_amd/photometric.py; SEMANTICS.md
+ * "Photometric loss") ---------------------------------------------------------------------------------------------------------------
+ * Up to GSR_MAX_PHOTO_VIEWS views of one size, each its own image x [C,H,W] fp32 (as the forward returns it: no stacking) and
+ * target y [C,H,W] fp32 or fp16 (widened exactly), C in 1..GSR_MAX_PHOTO_CHANNELS, any H, W >= 1:
+ *   loss[v] = l2 mean((x-y)^2) + l1 mean|x-y| + dssim (1 - mean(ssim_map(x, y)))        means over the view's C H W entries
+ *   ssim_map: window 11x11 Gaussian, sigma 1.5 (gsr_photo_window), zero padding 5, per channel, applied separably;
+ *             s = E[ab] - mu_a mu_b, C1 = 0.01^2, C2 = 0.03^2. round_image_to_half: x is rounded to fp16 (nearest even) on load
+ *             -- the refine steps' .to(torch.float16) -- and its gradient passes straight through.
+ * All per-pixel arithmetic is fp32 (NOT the reference's fp16 L2: SEMANTICS.md), every sum over pixels is in double in a fixed
+ * order: no atomics, the same bits on every run.
+ * gsr_photo_window    the 11 taps: exp(-(i-5)^2 / 4.5) in double, rounded to fp32, divided in fp32 by their fp32 sum. Host only.
+ * gsr_photo_forward   dssim != 0: one launch over (32x32 tile, channel, view) with the halo of x and y in LDS, then one small
+ *                     launch that adds the per-block partials. saved != NULL: also the planes dm/dmu_x, dm/ds_x, dm/ds_xy,
+ *                     [3][V,C,H,W] fp32, which the backward needs; NULL (no gradient wanted) skips the store.
+ *                     dssim == 0: the point-wise form, no halo and no saved planes (saved is not touched).
+ *                     loss [V]; terms [V,3] or NULL: the unweighted (L2, L1, D-SSIM) of every view (D-SSIM is NaN in the
+ *                     point-wise form, which does not evaluate it). scratch: gsr_photo_scratch_bytes(V, C, H, W) bytes, 16-byte
+ *                     aligned (0: the shape is not accepted); too small: GSR_ESCRATCH.
+ * gsr_photo_backward  one launch: dL_dimage[k] [C,H,W] (stored, not accumulated) = dL_dloss[k] (device memory, [V]) times the
+ *                     exact d loss[k] / dx; d|x-y|/dx at x == y is 0. No gradient goes to the targets. With dssim != 0 it reads
+ *                     the `saved` planes of the forward on the same views and weights.
+ * Both: enqueued on `stream`, no allocation, no host synchronisation (capturable into a hipGraph). Bad shapes and counts, NULL
+ * or misaligned (4 bytes; fp16 targets 2) pointers, all-zero or NaN weights and a missing `saved` with dssim != 0 in the backward:
+ * GSR_EINVAL before any HIP call. */
+#define GSR_MAX_PHOTO_VIEWS 16
+#define GSR_MAX_PHOTO_CHANNELS 4
+#define GSR_PHOTO_WINDOW 11
+typedef struct GsrPhotoViews {
+  int32_t n_views;                                   /* 1..GSR_MAX_PHOTO_VIEWS                                  */
+  int32_t channels;                                  /* 1..GSR_MAX_PHOTO_CHANNELS                               */
+  int32_t height, width;
+  int32_t target_is_half;                            /* != 0: the targets are fp16                              */
+  int32_t round_image_to_half;                       /* != 0: x is rounded to fp16 on load                      */
+  const float* image[GSR_MAX_PHOTO_VIEWS];           /* view k: [C,H,W]                                         */
+  const void* target[GSR_MAX_PHOTO_VIEWS];           /* view k: [C,H,W] fp32 or fp16                            */
+  float* dL_dimage[GSR_MAX_PHOTO_VIEWS];             /* view k: [C,H,W], written by the backward (unused by the forward) */
+} GsrPhotoViews;
+typedef struct GsrPhotoWeights {
+  float l2, l1, dssim;
+} GsrPhotoWeights;
+void gsr_photo_window(float* taps);
+size_t gsr_photo_scratch_bytes(int32_t n_views, int32_t channels, int32_t height, int32_t width);
+int gsr_photo_forward(const GsrPhotoViews* views, const GsrPhotoWeights* weights, float* loss, float* terms, float* saved,
+                      void* scratch, size_t scratch_bytes, void* stream);
+int gsr_photo_backward(const GsrPhotoViews* views, const GsrPhotoWeights* weights, const float* saved, const float* dL_dloss,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
