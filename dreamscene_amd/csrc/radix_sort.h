@@ -164,7 +164,11 @@ k_radix_scatter(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict
   __shared__ uint32_t wtot[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const uint64_t n = eff_count(n_dev, cap);
-  if ((uint64_t)blockIdx.x * (kSortThreads * ITEMS) >= n) return;
+  if ((uint64_t)blockIdx.x * (kSortThreads * ITEMS) >= n) {
+    // (workgroup 0 leaves here only for n == 0: the later passes read their count from *n_out, so it is stored all the same)
+    if (DROP && n_out && blockIdx.x == 0 && tid == 0) *n_out = 0;
+    return;
+  }
 #pragma unroll
   for (int w = 0; w < 4; ++w) wh[w][tid] = 0;
   {
@@ -454,7 +458,11 @@ k_os_pass(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__ val
   if (early_out && tile == 0 && tid == 0)
     __hip_atomic_store(early_out + blockIdx.y, *reinterpret_cast<const uint64_t*>(os + kOsEarlyN), __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_SYSTEM);
-  if ((uint64_t)tile * T >= n) return;     // (every later ticket is beyond n as well: nobody waits for this tile)
+  if ((uint64_t)tile * T >= n) {           // (every later ticket is beyond n as well: nobody waits for this tile)
+    // (ticket 0 leaves here only for n == 0: the later passes read their count from *n_out, so it is stored all the same)
+    if (DROP && n_out && tile == 0 && tid == 0) *n_out = 0;
+    return;
+  }
   // exclusive scan of the pass's global digit histogram: where digit d starts in the output
   uint32_t dbase;
   {
