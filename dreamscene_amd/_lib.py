@@ -23,6 +23,7 @@ class GsrView(C.Structure):
 
 
 GSR_MAX_MODELS = 16
+GSR_NOISE_SCALES, GSR_NOISE_SHS = 1, 2     # GsrScene.noise_flags
 GSR_PACKED_VIEW_FLOATS = 44
 GSR_PARTIAL_WORDS = 32     # 32-bit words per Gaussian of GsrGrads.partials (16 doubles, 12 used)
 
@@ -35,7 +36,8 @@ class GsrModel(C.Structure):
 class GsrScene(C.Structure):
     _fields_ = [("n_models", C.c_int32), ("reserved_", C.c_int32), ("models", GsrModel * GSR_MAX_MODELS),
                 ("scale_noise", _f), ("sh_noise", _f), ("scales_out", _f), ("rotations_out", _f),
-                ("opacities_out", _f)]
+                ("opacities_out", _f), ("noise_seed", C.c_uint64), ("noise_stream_dev", _f),
+                ("noise_stream", C.c_uint32), ("noise_flags", C.c_uint32)]
 
 
 class GsrModelGrads(C.Structure):
@@ -225,6 +227,7 @@ SYMBOLS = [
     ("gsr_densify_plan", C.c_int, [C.POINTER(GsrDensifyPlan), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("gsr_densify_plan_mask", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("gsr_densify_apply", C.c_int, [C.POINTER(GsrDensifyTable), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    ("gsr_noise_fill", C.c_int, [C.c_uint64, C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("gsr_place_scratch_bytes", C.c_size_t, [C.c_int32]),
     ("gsr_place", C.c_int, [C.POINTER(GsrPlacement), C.c_void_p, C.c_size_t, C.c_void_p]),
     ("gsr_frames_scratch_bytes", C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),

@@ -36,6 +36,10 @@ int check_scene(const GsrView* v, const GsrGaussians* g) {
   }
   if (total != (int64_t)v->P) return GSR_EINVAL;
   if (sc->rotations_out && !aligned16(sc->rotations_out)) return GSR_EINVAL;
+  // seeded noise: known flags only, and a noise comes from its tensor or from the generator, not both
+  if (sc->noise_flags & ~(GSR_NOISE_SCALES | GSR_NOISE_SHS)) return GSR_EINVAL;
+  if ((sc->noise_flags & GSR_NOISE_SCALES) && sc->scale_noise) return GSR_EINVAL;
+  if ((sc->noise_flags & GSR_NOISE_SHS) && sc->sh_noise) return GSR_EINVAL;
   return GSR_OK;
 }
 
@@ -236,7 +240,7 @@ int gsr_forward_project_batch(int32_t n_views, const GsrView* views, const GsrGa
     bool same_view_consts = true;
     for (int k = 1; k < n_views; ++k)
       same_view_consts = same_view_consts && views[k].scale_modifier == v0.scale_modifier;
-    if (n_views > 1 && same_view_consts && gsr_preprocess_views_supported(v0, *g)) {
+    if (n_views > 1 && same_view_consts && gsr_preprocess_views_supported(v0, *g) && gsr_batch_noise_fits(n_views, gs)) {
       const int rc = gsr_launch_preprocess_views(n_views, views, gs, geoms, stream);
       if (rc) return rc;
     } else {
@@ -444,7 +448,8 @@ int gsr_backward_views(int32_t n_views, const GsrView* views, const GsrGaussians
     for (int k = 0; k < n_views; ++k)
       for (int j = 0; j < k; ++j)
         if (!outs[k].dL_dscales || outs[k].dL_dscales == outs[j].dL_dscales) return GSR_EINVAL;
-  const bool fused = n_views > 1 && gsr_preprocess_bwd_views_supported(views[0], *g, outs[0]);
+  const bool fused = n_views > 1 && gsr_preprocess_bwd_views_supported(views[0], *g, outs[0]) &&
+                     gsr_batch_noise_fits(n_views, gs);
   if (per_view_scales && !fused) return GSR_EINVAL;   // per-view scales are only supported by the fused pass
   // the views' partials usually are the rows of one [n_views, P, 32] tensor: one clear instead of n_views
   const size_t pbytes = (size_t)views[0].P * GSR_PARTIAL_WORDS * sizeof(float);
@@ -512,6 +517,16 @@ int gsr_backward_views(int32_t n_views, const GsrView* views, const GsrGaussians
       }
   }
   return GSR_OK;
+}
+
+int gsr_noise_fill(uint64_t seed, uint32_t stream, const uint32_t* stream_dev, int32_t P, int32_t K, float* scale_noise,
+                   float* sh_noise, void* hip_stream) {
+  if (P < 0) return GSR_EINVAL;
+  if (K < 1 || K > 16) return GSR_EINVAL;
+  if (!scale_noise && !sh_noise) return GSR_EINVAL;
+  if (P == 0) return GSR_OK;
+  GsrDeviceGuard dev(scale_noise ? scale_noise : sh_noise);
+  return gsr_launch_noise_fill(seed, stream, stream_dev, P, K, scale_noise, sh_noise, (hipStream_t)hip_stream);
 }
 
 }  // extern "C"

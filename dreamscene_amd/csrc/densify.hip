@@ -18,6 +18,7 @@
 #include <math.h>
 
 #include "gsr_common.h"
+#include "gsr_rng.h"
 
 namespace {
 
@@ -170,20 +171,7 @@ k_densify_index(const uint8_t* __restrict__ flags, const uint32_t* __restrict__ 
     }
 }
 
-// ---- Philox-4x32-10 (Salmon et al., SC'11) + Box-Muller: three standard normals as a pure function of (seed, row, copy)
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                              uint32_t out[4]) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-    const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-    const uint32_t n0 = h1 ^ c1 ^ k0, n2 = h0 ^ c3 ^ k1;
-    c0 = n0; c1 = l1; c2 = n2; c3 = l0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-__device__ __forceinline__ float u01(uint32_t x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }   // (0, 1)
+// ---- three standard normals as a pure function of (seed, row, copy): Philox-4x32-10 + Box-Muller (gsr_rng.h)
 __device__ __forceinline__ void normals3(uint64_t seed, uint32_t row, uint32_t copy, float n[3]) {
   uint32_t r[4];
   philox4x32_10(row, copy, 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);

@@ -8,8 +8,11 @@
 // preprocess.hip (K1)
 int gsr_launch_preprocess(const GsrView& v, const GsrGaussians& g, GsrGeom& geom, hipStream_t stream);
 bool gsr_preprocess_views_supported(const GsrView& v, const GsrGaussians& g);
+bool gsr_batch_noise_fits(int n_views, const GsrGaussians* gs);   // seeded noise of a batch: what the views kernels can carry
 int gsr_launch_preprocess_views(int n_views, const GsrView* views, const GsrGaussians* gs, GsrGeom* geoms,
                                 hipStream_t stream);
+int gsr_launch_noise_fill(uint64_t seed, uint32_t stream, const uint32_t* stream_dev, int32_t P, int32_t K,
+                          float* scale_noise, float* sh_noise, hipStream_t hip_stream);
 
 // preprocess_bwd.hip (K8)
 bool gsr_preprocess_bwd_views_supported(const GsrView& v, const GsrGaussians& g, const GsrGrads& out);

@@ -2,6 +2,7 @@
 // cov3D, the EWA chain, the SH basis, the input staging and the host helpers of both launchers.
 #pragma once
 #include "gsr_common.h"
+#include "gsr_rng.h"
 #include <type_traits>
 
 namespace {
@@ -36,6 +37,120 @@ __device__ __forceinline__ void load_view_const(const float* viewmatrix, const f
   for (int i = 0; i < 3; ++i) c.cam[i] = cam[i];
 }
 
+constexpr float kSqrtPoint2 = 0.44721359549995793f;   // 0.2 ** 0.5 (scene_render's augmentations, below)
+
+// ---- Where the N(0,1) samples of the scene path's augmentations come from (GsrScene): a tensor, the generator (gsr_rng.h), or
+// nowhere. Passed by value in the kernel arguments; K8 gets what K1 got, so it regenerates exactly what K1 saw.
+struct NoiseSrc {
+  const float* scale;           // [P,3] samples or NULL
+  const float* sh;              // [P,K,3] samples or NULL
+  const uint32_t* stream_dev;   // NULL, or device u32[1]: the stream id, read when the kernel runs
+  uint32_t seed_lo, seed_hi, stream, flags;   // flags: GSR_NOISE_* -- that noise comes from the generator
+};
+// GEN: the kernel is instantiated for the generator. The instantiations without it hold none of its code (K1 is
+// register-sensitive: DESIGN.md), and flags are only honoured with it: the launchers pick GEN whenever a flag is set.
+template <bool GEN>
+__device__ __forceinline__ bool noise_has_scale(const NoiseSrc& z) {
+  return z.scale != nullptr || (GEN && (z.flags & GSR_NOISE_SCALES));
+}
+template <bool GEN>
+__device__ __forceinline__ bool noise_has_sh(const NoiseSrc& z) {
+  return z.sh != nullptr || (GEN && (z.flags & GSR_NOISE_SHS));
+}
+template <bool GEN>
+__device__ __forceinline__ uint32_t noise_stream(const NoiseSrc& z) {
+  if constexpr (GEN) {
+    if (z.stream_dev) return *(const __attribute__((address_space(4))) uint32_t*)(uintptr_t)z.stream_dev;   // (scalar load)
+    return z.stream;
+  }
+  return 0u;
+}
+// the three scale normals of Gaussian i (zeros without scale noise)
+template <bool GEN>
+__device__ __forceinline__ void noise_scale3(const NoiseSrc& z, uint32_t stream, int64_t i, float n[3]) {
+  if (GEN && (z.flags & GSR_NOISE_SCALES)) {
+    float b[4];
+    noise_block(z.seed_lo, z.seed_hi, stream, kNoiseTagScale, (uint32_t)i, 0u, b);
+    n[0] = b[0]; n[1] = b[1]; n[2] = b[2];
+  } else {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) n[k] = z.scale ? z.scale[3 * i + k] : 0.f;
+  }
+}
+// the SH normals 4j .. 4j+3 of Gaussian i's flattened [K,3] row of F floats (past the row: zeros); needs noise_has_sh
+template <bool GEN>
+__device__ __forceinline__ void noise_sh4(const NoiseSrc& z, uint32_t stream, int64_t i, int j, int F, float n[4]) {
+  if (GEN && (z.flags & GSR_NOISE_SHS)) {
+    noise_block(z.seed_lo, z.seed_hi, stream, kNoiseTagSh, (uint32_t)i, (uint32_t)j, n);
+  } else {
+    const float* row = z.sh + (size_t)i * F + 4 * j;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) n[e] = (4 * j + e < F) ? row[e] : 0.f;
+  }
+}
+// sh_e <- sh_e + n_e * (sqrt(0.2) * sh_e) over a row of F coefficients, the normals taken a block of four at a time: a register
+// row (compile-time F, constant indices) ...
+template <bool GEN, int F>
+__device__ __forceinline__ void sh_noise_apply(const NoiseSrc& z, uint32_t stream, int64_t i, float* sh) {
+#pragma unroll
+  for (int j = 0; j < (F + 3) / 4; ++j) {
+    float n[4];
+    noise_sh4<GEN>(z, stream, i, j, F, n);
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (4 * j + e < F) sh[4 * j + e] = sh[4 * j + e] + n[e] * (kSqrtPoint2 * sh[4 * j + e]);
+  }
+}
+// ... or the lane's LDS row (runtime F)
+template <bool GEN>
+__device__ __forceinline__ void sh_noise_apply_n(const NoiseSrc& z, uint32_t stream, int64_t i, int F, float* sh) {
+#pragma unroll 1
+  for (int j = 0; 4 * j < F; ++j) {
+    float n[4];
+    noise_sh4<GEN>(z, stream, i, j, F, n);
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (4 * j + e < F) sh[4 * j + e] = sh[4 * j + e] + n[e] * (kSqrtPoint2 * sh[4 * j + e]);
+  }
+}
+// K8: dL/dsh_e <- dL/dsh_e * (1 + sqrt(0.2) n_e) over the first F_active entries of the lane's LDS row of F
+template <bool GEN>
+__device__ __forceinline__ void sh_noise_chain_n(const NoiseSrc& z, uint32_t stream, int64_t i, int F, int F_active, float* dsh) {
+#pragma unroll 1
+  for (int j = 0; 4 * j < F_active; ++j) {
+    float n[4];
+    noise_sh4<GEN>(z, stream, i, j, F, n);
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (4 * j + e < F_active) dsh[4 * j + e] = dsh[4 * j + e] * (1.0f + kSqrtPoint2 * n[e]);
+  }
+}
+// The noise sources of the views of a batched launch, compact: K8's scene kernel takes SceneTab, SceneGradTab, K8Views and
+// GsrGrads by value, and a NoiseSrc per view would carry its kernel arguments past 4 KB. The views of a batch therefore share the
+// seed, and their device stream words, when given, are consecutive (view k reads stream_dev[k]); a batch that does not fit runs
+// view by view (gsr_batch_noise_fits).
+struct NoiseViews {
+  const float* scale[GSR_MAX_BATCH_VIEWS];
+  const float* sh[GSR_MAX_BATCH_VIEWS];
+  const uint32_t* stream_dev;
+  uint32_t seed_lo, seed_hi;
+  uint32_t stream[GSR_MAX_BATCH_VIEWS];
+  uint8_t flags[GSR_MAX_BATCH_VIEWS];
+  __device__ __forceinline__ NoiseSrc view(int k) const {
+    NoiseSrc z;
+    z.scale = scale[k]; z.sh = sh[k]; z.stream_dev = (stream_dev && flags[k]) ? stream_dev + k : nullptr;
+    z.seed_lo = seed_lo; z.seed_hi = seed_hi; z.stream = stream[k]; z.flags = flags[k];
+    return z;
+  }
+};
+static NoiseSrc noise_src(const GsrScene& sc) {
+  NoiseSrc z;
+  z.scale = sc.scale_noise; z.sh = sc.sh_noise; z.stream_dev = sc.noise_stream_dev;
+  z.seed_lo = (uint32_t)sc.noise_seed; z.seed_hi = (uint32_t)(sc.noise_seed >> 32);
+  z.stream = sc.noise_stream; z.flags = sc.noise_flags;
+  return z;
+}
+
 // ---- multi-model ("scene") input: GsrScene flattened for the kernels (passed by value in the kernel arguments).
 // A workgroup never straddles two models: model m owns the workgroups [fblk[m], fblk[m+1]) and its Gaussians keep
 // their place first[m] + row in the concatenated index space every other kernel works in.
@@ -49,8 +164,7 @@ struct SceneTab {
   const float* opacity[GSR_MAX_MODELS];
   const float* dc[GSR_MAX_MODELS];
   const float* rest[GSR_MAX_MODELS];
-  const float* scale_noise;
-  const float* sh_noise;
+  NoiseSrc noise;
   float* scales_out;
   float* rotations_out;
   float* opacities_out;
@@ -103,7 +217,6 @@ __device__ __forceinline__ Rows resolve_rows(const TAB& sc, int P) {
 }
 
 // The activations of GaussianModel (gs_renderer.py:464-488) and scene_render's augmentations (scene_gaussian.py:844-852)
-constexpr float kSqrtPoint2 = 0.44721359549995793f;   // 0.2 ** 0.5
 struct ActScale { float act, pre, out; };              // exp(raw); after the noise; after the clamp
 __device__ __forceinline__ ActScale act_scale(float raw, bool noisy, float n) {
   ActScale a;
@@ -359,7 +472,7 @@ static uint32_t scene_tables(const GsrScene& sc, const GsrSceneGrads* sgr, Scene
     }
   }
   for (int m = sc.n_models; m <= GSR_MAX_MODELS; ++m) { t.first[m] = first; t.fblk[m] = blk; }
-  t.scale_noise = sc.scale_noise; t.sh_noise = sc.sh_noise;
+  t.noise = noise_src(sc);
   t.scales_out = sc.scales_out; t.rotations_out = sc.rotations_out; t.opacities_out = sc.opacities_out;
   return (uint32_t)blk;
 }
@@ -368,7 +481,15 @@ static uint32_t scene_tables(const GsrScene& sc, const GsrSceneGrads* sgr, Scene
 template <class VB>
 static void fill_view_fields(VB& vb, int n_views, const GsrView* views, const GsrGaussians* gs) {
   for (int k = 0; k < n_views; ++k) {
-    if (gs[0].scene) { vb.scale_noise[k] = gs[k].scene->scale_noise; vb.sh_noise[k] = gs[k].scene->sh_noise; }
+    if (gs[0].scene) {
+      const GsrScene& sc = *gs[k].scene;
+      vb.noise.scale[k] = sc.scale_noise; vb.noise.sh[k] = sc.sh_noise;
+      vb.noise.stream[k] = sc.noise_stream; vb.noise.flags[k] = (uint8_t)sc.noise_flags;
+      if (sc.noise_flags) {     // (the same for every view that has flags: gsr_batch_noise_fits)
+        vb.noise.seed_lo = (uint32_t)sc.noise_seed; vb.noise.seed_hi = (uint32_t)(sc.noise_seed >> 32);
+        vb.noise.stream_dev = sc.noise_stream_dev ? sc.noise_stream_dev - k : nullptr;
+      }
+    }
     vb.scales[k] = gs[k].scales;
     if (gs[k].scales != gs[0].scales) vb.per_view_scales = 1;
     vb.viewmatrix[k] = views[k].viewmatrix; vb.projmatrix[k] = views[k].projmatrix; vb.campos[k] = views[k].campos;
@@ -388,6 +509,12 @@ static int launch_sh(int K, F&& f) {
 // the single-view kernels: compile-time strides read their rows directly (no LDS); every other stride runs the generic
 // KT = 0 kernel, which stages the rows through LDS
 static int fixed_sh(int K) { return K == 16 || K == 9 || K == 4 || K == 1 ? K : 0; }
+// does any of the views' scenes draw noise from the generator? (then the launchers take the GEN instantiations)
+static bool scene_noise_generated(int n_views, const GsrGaussians* gs) {
+  bool gen = false;
+  for (int k = 0; k < n_views; ++k) gen = gen || (gs[k].scene && gs[k].scene->noise_flags != 0u);
+  return gen;
+}
 // a runtime flag -> std::true_type / std::false_type
 template <class F>
 static void with_flag(bool b, F&& f) {

@@ -89,7 +89,8 @@ __device__ __forceinline__ void store_view_ints(int32_t* radii, uint32_t* tiles_
 // the Gaussian is in front of a camera -- two memory round trips per wave instead of three, the second one under the footprint
 // arithmetic. Measured (round 4, one call, same box): k_preprocess_views<16> 65.8 -> 64.7 us at C3, k_preprocess<16> 30.9 ->
 // 29.9 us per view: the kernel is not bound by its round trips (VALU 50 % busy, 4 TB/s of mixed read / write traffic).
-template <int KT, bool SCENE = false, typename TAB = NoScene>
+// GEN (scene only): the augmentation noise may come from the generator (NoiseSrc, gsr_project.h) instead of a tensor.
+template <int KT, bool SCENE = false, typename TAB = NoScene, bool GEN = false>
 __global__ void __launch_bounds__(256)
 k_preprocess(const GsrView v, const GsrGaussians g, const TAB sc, float* __restrict__ splat,
              int32_t* __restrict__ radii, uint32_t* __restrict__ tiles_touched, uint32_t* __restrict__ depth_keys,
@@ -104,8 +105,10 @@ k_preprocess(const GsrView v, const GsrGaussians g, const TAB sc, float* __restr
   const int64_t i = rw.i, row = rw.row, wave_first = rw.wave_row;
   const int n_valid = rw.n_valid;
   const float *p_xyz = g.means3D, *p_scale = g.scales, *p_rot = g.rotations, *p_opac = g.opacities;
+  [[maybe_unused]] uint32_t nstream = 0u;
   if constexpr (SCENE) {
     p_xyz = sc.xyz[rw.m]; p_scale = sc.scaling[rw.m]; p_rot = sc.rotation[rw.m]; p_opac = sc.opacity[rw.m];
+    nstream = noise_stream<GEN>(sc.noise);
   }
   const int gx = (W + GSR_TILE - 1) / GSR_TILE, gy = (H + GSR_TILE - 1) / GSR_TILE;
   const ViewDyn vd = view_dyn(v.dynamic, v.tanfovx, v.tanfovy, v.sh_degree);
@@ -142,11 +145,11 @@ k_preprocess(const GsrView v, const GsrGaussians g, const TAB sc, float* __restr
     if constexpr (SCENE) {
       // activated values the caller gets back (scene_render returns the augmented scales, scene_gaussian.py:892)
       if (sc.scales_out) {
+        float n[3];
+        noise_scale3<GEN>(sc.noise, nstream, i, n);
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          const float n = sc.scale_noise ? sc.scale_noise[3 * i + k] : 0.f;
-          sc.scales_out[3 * i + k] = act_scale(p_scale[3 * row + k], sc.scale_noise != nullptr, n).out;
-        }
+        for (int k = 0; k < 3; ++k)
+          sc.scales_out[3 * i + k] = act_scale(p_scale[3 * row + k], noise_has_scale<GEN>(sc.noise), n[k]).out;
       }
       if (sc.rotations_out) {
         const float4 q = *reinterpret_cast<const float4*>(p_rot + 4 * row);
@@ -175,11 +178,10 @@ k_preprocess(const GsrView v, const GsrGaussians g, const TAB sc, float* __restr
           q = *reinterpret_cast<const float4*>(p_rot + 4 * row);
         }
         if constexpr (SCENE) {
+          float n[3];
+          noise_scale3<GEN>(sc.noise, nstream, i, n);
 #pragma unroll
-          for (int k = 0; k < 3; ++k) {
-            const float n = sc.scale_noise ? sc.scale_noise[3 * i + k] : 0.f;
-            sa[k] = act_scale(sa[k], sc.scale_noise != nullptr, n).out;
-          }
+          for (int k = 0; k < 3; ++k) sa[k] = act_scale(sa[k], noise_has_scale<GEN>(sc.noise), n[k]).out;
           const float nrm = act_quat_norm(q);
           q = make_float4(q.x / nrm, q.y / nrm, q.z / nrm, q.w / nrm);
         }
@@ -210,9 +212,11 @@ k_preprocess(const GsrView v, const GsrGaussians g, const TAB sc, float* __restr
       float shr[F];
       load_row<3>(sc.dc[rw.m] + row * 3, shr);
       if constexpr (KT > 1) load_row<F - 3>(sc.rest[rw.m] + row * (F - 3), shr + 3);
-      if (sc.sh_noise) {
+      if constexpr (GEN) {
+        if (noise_has_sh<GEN>(sc.noise)) sh_noise_apply<GEN, F>(sc.noise, nstream, i, shr);
+      } else if (sc.noise.sh) {
         float nz[F];
-        load_row<F>(sc.sh_noise + (size_t)i * F, nz);
+        load_row<F>(sc.noise.sh + (size_t)i * F, nz);
 #pragma unroll
         for (int k = 0; k < F; ++k) shr[k] = shr[k] + nz[k] * (kSqrtPoint2 * shr[k]);
       }
@@ -252,12 +256,16 @@ k_preprocess(const GsrView v, const GsrGaussians g, const TAB sc, float* __restr
         stage_rows_in(sc.dc[rw.m] + wave_first * 3, 3, 0, sh_lds_stride(K), n_valid, vmask, lw);
         if (K > 1) stage_rows_in(sc.rest[rw.m] + wave_first * (3 * K - 3), 3 * K - 3, 3, sh_lds_stride(K), n_valid, vmask, lw);
       }
-      if (sc.sh_noise && vis) {
+      if (noise_has_sh<GEN>(sc.noise) && vis) {
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         float* shw = lw + lane * sh_lds_stride(K);
-        const float* nz = sc.sh_noise + (size_t)i * (3 * K);
-        for (int k = 0; k < 3 * K; ++k) shw[k] = shw[k] + nz[k] * (kSqrtPoint2 * shw[k]);
+        if constexpr (GEN) {
+          sh_noise_apply_n<GEN>(sc.noise, nstream, i, 3 * K, shw);
+        } else {
+          const float* nz = sc.noise.sh + (size_t)i * (3 * K);
+          for (int k = 0; k < 3 * K; ++k) shw[k] = shw[k] + nz[k] * (kSqrtPoint2 * shw[k]);
+        }
       }
     } else if (vmask) stage_sh_in<KT>(g.shs, wave_first, n_valid, K, vmask, lw);
     __builtin_amdgcn_wave_barrier();
@@ -304,8 +312,7 @@ struct K1Views {
   int32_t per_view_scales;
   const float* scales[GSR_MAX_BATCH_VIEWS];
   // scene input (raw leaves): per-view noise samples and the per-view activated scales handed back to the caller
-  const float* scale_noise[GSR_MAX_BATCH_VIEWS];
-  const float* sh_noise[GSR_MAX_BATCH_VIEWS];
+  NoiseViews noise;
   float* scales_out[GSR_MAX_BATCH_VIEWS];
   float* splat[GSR_MAX_BATCH_VIEWS];
   int32_t* radii[GSR_MAX_BATCH_VIEWS];
@@ -418,7 +425,7 @@ k_preprocess_views(const GsrView v, const GsrGaussians g, const K1Views vb) {
 
 // K1 over several views of a SCENE (raw leaves of several models, activations fused; see k_preprocess<K, true>): the
 // raw rows are read once, exp / normalize / sigmoid are applied once, the per-view scale noise (and SH noise) per view.
-template <int KT>
+template <int KT, bool GEN = false>
 __global__ void __launch_bounds__(256)
 k_preprocess_views_scene(const GsrView v, const SceneTab sc, const K1Views vb) {
   constexpr int F = 3 * KT;
@@ -438,11 +445,14 @@ k_preprocess_views_scene(const GsrView v, const SceneTab sc, const K1Views vb) {
   float R[9], c6[6], shr[F];
   float opac = 0.f, tau = -1.f;
   for (int vv = 0; vv < vb.nv; ++vv) {
-    const float* sn = vb.scale_noise[vv];
-    float sa[3];
+    const NoiseSrc nz = vb.noise.view(vv);
+    const uint32_t nstream = noise_stream<GEN>(nz);
+    const bool sn = noise_has_scale<GEN>(nz);
+    float sa[3], nsc[3];
+    noise_scale3<GEN>(nz, nstream, i, nsc);
 #pragma unroll
     for (int k = 0; k < 3; ++k)
-      sa[k] = sn ? fmaxf(aact[k] + sn[3 * i + k] * ((kSqrtPoint2 * aact[k]) / 4.0f), 0.0f) : aact[k];
+      sa[k] = sn ? fmaxf(aact[k] + nsc[k] * ((kSqrtPoint2 * aact[k]) / 4.0f), 0.0f) : aact[k];
     if (vb.scales_out[vv]) {
       float* so = vb.scales_out[vv];
       so[3 * i] = sa[0]; so[3 * i + 1] = sa[1]; so[3 * i + 2] = sa[2];
@@ -483,11 +493,17 @@ k_preprocess_views_scene(const GsrView v, const SceneTab sc, const K1Views vb) {
       float b[16];
       sh_basis(vd.sh_degree, d.x, d.y, d.z, b);
       float acc[3];
-      if (vb.sh_noise[vv]) {
+      if (noise_has_sh<GEN>(nz)) {
         float shv[F];
-        const float* nz = vb.sh_noise[vv] + (size_t)i * F;
+        if constexpr (GEN) {
 #pragma unroll
-        for (int k = 0; k < F; ++k) shv[k] = shr[k] + nz[k] * (kSqrtPoint2 * shr[k]);
+          for (int k = 0; k < F; ++k) shv[k] = shr[k];
+          sh_noise_apply<GEN, F>(nz, nstream, i, shv);
+        } else {
+          const float* nr = nz.sh + (size_t)i * F;
+#pragma unroll
+          for (int k = 0; k < F; ++k) shv[k] = shr[k] + nr[k] * (kSqrtPoint2 * shr[k]);
+        }
         sh_colour_n<KT>(vd.sh_degree, shv, b, acc);
       } else {
         sh_colour_n<KT>(vd.sh_degree, shr, b, acc);
@@ -508,7 +524,47 @@ k_preprocess_views_scene(const GsrView v, const SceneTab sc, const K1Views vb) {
   }
 }
 
+// The tensors the generator stands for (gsr_noise_fill): one thread per Philox block -- block 0 of a Gaussian is its scale
+// noise, block 1 + j is block j of its SH noise. The values are formed by the function K1 and K8 call (noise_block), under
+// the same -ffp-contract=off: a scene fed with these tensors sees the same bits.
+__global__ void __launch_bounds__(256)
+k_noise_fill(const NoiseSrc z, const int64_t P, const int F, float* __restrict__ scale_noise, float* __restrict__ sh_noise) {
+  const int nb = 1 + (F + 3) / 4;
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t i = t / nb;
+  const int b = (int)(t - i * nb);
+  if (i >= P) return;
+  const uint32_t stream = noise_stream<true>(z);
+  float n[4];
+  if (b == 0) {
+    if (!scale_noise) return;
+    noise_block(z.seed_lo, z.seed_hi, stream, kNoiseTagScale, (uint32_t)i, 0u, n);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) scale_noise[3 * i + k] = n[k];
+  } else {
+    if (!sh_noise) return;
+    const int j = b - 1;
+    noise_block(z.seed_lo, z.seed_hi, stream, kNoiseTagSh, (uint32_t)i, (uint32_t)j, n);
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+      if (4 * j + e < F) sh_noise[i * F + 4 * j + e] = n[e];
+  }
+}
+
 }  // namespace
+
+int gsr_launch_noise_fill(uint64_t seed, uint32_t stream, const uint32_t* stream_dev, int32_t P, int32_t K,
+                          float* scale_noise, float* sh_noise, hipStream_t hip_stream) {
+  NoiseSrc z = NoiseSrc{};
+  z.stream_dev = stream_dev; z.stream = stream;
+  z.seed_lo = (uint32_t)seed; z.seed_hi = (uint32_t)(seed >> 32);
+  const int F = 3 * K;
+  const int64_t threads = (int64_t)P * (1 + (F + 3) / 4);
+  hipLaunchKernelGGL(k_noise_fill, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, hip_stream, z, (int64_t)P, F,
+                     scale_noise, sh_noise);
+  GSR_HIP(hipGetLastError());
+  return GSR_OK;
+}
 
 uint32_t* gsr_depth_keys(const GsrGeom& geom, int32_t P);   // binning.hip: first key buffer of the depth sort
 uint32_t* gsr_depth_sort_state(const GsrGeom& geom, int32_t P, uint32_t* words);   // binning.hip: state K1 clears for the sort
@@ -522,9 +578,11 @@ int gsr_launch_preprocess(const GsrView& v, const GsrGaussians& g, GsrGeom& geom
     const uint32_t nbs = scene_tables(*g.scene, nullptr, t, gt);
     const size_t lds = gsr_preprocess_lds_bytes(v.sh_stride);
     return launch_sh<16, 9, 4, 1, 0>(fixed_sh(v.sh_stride), [&](auto kt) {
-      hipLaunchKernelGGL((k_preprocess<kt, true, SceneTab>), dim3(nbs), dim3(256), kt > 0 ? 0 : lds, stream, v, g, t,
-                         geom.splat, geom.radii, geom.tiles_touched, gsr_depth_keys(geom, v.P), gsr_tile_rects(geom, v.P),
-                         ss, ss_words);
+      with_flag(scene_noise_generated(1, &g), [&](auto gen) {
+        hipLaunchKernelGGL((k_preprocess<kt, true, SceneTab, gen>), dim3(nbs), dim3(256), kt > 0 ? 0 : lds, stream, v, g, t,
+                           geom.splat, geom.radii, geom.tiles_touched, gsr_depth_keys(geom, v.P),
+                           gsr_tile_rects(geom, v.P), ss, ss_words);
+      });
     });
   }
   const uint32_t nb = gsr_num_blocks(v.P);
@@ -541,6 +599,20 @@ bool gsr_preprocess_views_supported(const GsrView& v, const GsrGaussians& g) {
   if (g.scene) return K == 1 || K == 4 || K == 9 || K == 16;
   return g.shs && !g.scene && g.scales && g.rotations && !g.cov3D_precomp && !g.colors_precomp &&
          (K == 1 || K == 4 || K == 9 || K == 16);
+}
+
+// The generator parameters of a batch travel compactly (NoiseViews): one seed, and device stream words that are consecutive.
+bool gsr_batch_noise_fits(int n_views, const GsrGaussians* gs) {
+  const GsrScene* first = nullptr;
+  int kf = 0;
+  for (int k = 0; k < n_views; ++k) {
+    const GsrScene* sc = gs[k].scene;
+    if (!sc || !sc->noise_flags) continue;
+    if (!first) { first = sc; kf = k; continue; }
+    if (sc->noise_seed != first->noise_seed || (sc->noise_stream_dev != nullptr) != (first->noise_stream_dev != nullptr)) return false;
+    if (sc->noise_stream_dev && sc->noise_stream_dev != first->noise_stream_dev + (k - kf)) return false;
+  }
+  return true;
 }
 
 int gsr_launch_preprocess_views(int n_views, const GsrView* views, const GsrGaussians* gs, GsrGeom* geoms,
@@ -560,7 +632,9 @@ int gsr_launch_preprocess_views(int n_views, const GsrView* views, const GsrGaus
     SceneTab t; SceneGradTab gt;
     const uint32_t nbs = scene_tables(*g.scene, nullptr, t, gt);
     return launch_sh<16, 9, 4, 1>(v.sh_stride, [&](auto kt) {
-      hipLaunchKernelGGL(k_preprocess_views_scene<kt>, dim3(nbs), dim3(256), 0, stream, v, t, vb);
+      with_flag(scene_noise_generated(n_views, gs), [&](auto gen) {
+        hipLaunchKernelGGL((k_preprocess_views_scene<kt, gen>), dim3(nbs), dim3(256), 0, stream, v, t, vb);
+      });
     });
   }
   const uint32_t nb = gsr_num_blocks(v.P);

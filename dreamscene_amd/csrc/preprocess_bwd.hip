@@ -239,7 +239,8 @@ __device__ __forceinline__ void partial_zero(float* __restrict__ partials, int64
 // --------------------------------------------------------------------------------------------------------- K8
 // partials [P,16 doubles] from K7 (see above): S1 = sum q u, S2 = sum q v, S3 = sum q u^2, S4 = sum q u v, S5 = sum q v^2
 // [(u, v) = -conic d], dL/dopacity, dL/dr, dL/dg, dL/db, dL/ddepth; q = dL/dG * G
-template <int KT, bool SCENE = false, typename TAB = NoScene, typename GTAB = NoScene>
+// GEN (scene only): the noise K1 drew from the generator is regenerated here (NoiseSrc, gsr_project.h).
+template <int KT, bool SCENE = false, typename TAB = NoScene, typename GTAB = NoScene, bool GEN = false>
 __global__ void __launch_bounds__(256)
 k_preprocess_bwd(const GsrView v, const GsrGaussians g, const TAB sc, const GTAB sg,
                  const int32_t* __restrict__ radii, const float* __restrict__ partials, const GsrGrads out) {
@@ -252,7 +253,11 @@ k_preprocess_bwd(const GsrView v, const GsrGaussians g, const TAB sc, const GTAB
   const int64_t i = rw.i, row = rw.row, wave_first = rw.wave_row;
   const int n_valid = rw.n_valid;
   const float *p_xyz = g.means3D, *p_scale = g.scales, *p_rot = g.rotations;
-  if constexpr (SCENE) { p_xyz = sc.xyz[rw.m]; p_scale = sc.scaling[rw.m]; p_rot = sc.rotation[rw.m]; }
+  [[maybe_unused]] uint32_t nstream = 0u;
+  if constexpr (SCENE) {
+    p_xyz = sc.xyz[rw.m]; p_scale = sc.scaling[rw.m]; p_rot = sc.rotation[rw.m];
+    nstream = noise_stream<GEN>(sc.noise);
+  }
   const float fx = (float)W / (2.0f * vd.tanfovx), fy = (float)H / (2.0f * vd.tanfovy);
   const float limx = 1.3f * vd.tanfovx, limy = 1.3f * vd.tanfovy;
   const float mod = v.scale_modifier;
@@ -301,9 +306,13 @@ k_preprocess_bwd(const GsrView v, const GsrGaussians g, const TAB sc, const GTAB
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
       }
-      if (sc.sh_noise && vis) {   // the augmented coefficients K1 saw
-        const float* nz = sc.sh_noise + (size_t)i * (3 * K);
-        for (int k = 0; k < 3 * K; ++k) sh[k] = sh[k] + nz[k] * (kSqrtPoint2 * sh[k]);
+      if (noise_has_sh<GEN>(sc.noise) && vis) {   // the augmented coefficients K1 saw
+        if constexpr (GEN) {
+          sh_noise_apply_n<GEN>(sc.noise, nstream, i, 3 * K, sh);
+        } else {
+          const float* nz = sc.noise.sh + (size_t)i * (3 * K);
+          for (int k = 0; k < 3 * K; ++k) sh[k] = sh[k] + nz[k] * (kSqrtPoint2 * sh[k]);
+        }
       }
     } else if constexpr (KT > 0 && (3 * KT) % 4 == 0) {
       // compile-time stride: each lane pulls its own row (as K1 does) and parks it in its LDS row; LDS is still
@@ -354,9 +363,13 @@ k_preprocess_bwd(const GsrView v, const GsrGaussians g, const TAB sc, const GTAB
 #undef GSR_SH_BWD_BAND
       for (int k = 3 * nb; k < 3 * K; ++k) sh[k] = 0.f;
       if constexpr (SCENE) {
-        if (sc.sh_noise) {   // d(sh + n c sh)/dsh = 1 + c n
-          const float* nz = sc.sh_noise + (size_t)i * (3 * K);
-          for (int k = 0; k < 3 * nb; ++k) sh[k] = sh[k] * (1.0f + kSqrtPoint2 * nz[k]);
+        if (noise_has_sh<GEN>(sc.noise)) {   // d(sh + n c sh)/dsh = 1 + c n
+          if constexpr (GEN) {
+            sh_noise_chain_n<GEN>(sc.noise, nstream, i, 3 * K, 3 * nb, sh);
+          } else {
+            const float* nz = sc.noise.sh + (size_t)i * (3 * K);
+            for (int k = 0; k < 3 * nb; ++k) sh[k] = sh[k] * (1.0f + kSqrtPoint2 * nz[k]);
+          }
         }
       }
       float ddx, ddy, ddz;
@@ -402,12 +415,13 @@ k_preprocess_bwd(const GsrView v, const GsrGaussians g, const TAB sc, const GTAB
       q = *reinterpret_cast<const float4*>(p_rot + 4 * row);
       if constexpr (SCENE) {
         qraw = q;
+        float n[3];
+        noise_scale3<GEN>(sc.noise, nstream, i, n);
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-          const float n = sc.scale_noise ? sc.scale_noise[3 * i + k] : 0.f;
-          const ActScale a = act_scale(sa[k], sc.scale_noise != nullptr, n);
+          const ActScale a = act_scale(sa[k], noise_has_scale<GEN>(sc.noise), n[k]);
           sa[k] = a.out;
-          dsc_draw[k] = scale_draw(a.act, a.pre, sc.scale_noise != nullptr, n);
+          dsc_draw[k] = scale_draw(a.act, a.pre, noise_has_scale<GEN>(sc.noise), n[k]);
         }
         qnorm = act_quat_norm(q);
         q = make_float4(q.x / qnorm, q.y / qnorm, q.z / qnorm, q.w / qnorm);
@@ -451,12 +465,13 @@ k_preprocess_bwd(const GsrView v, const GsrGaussians g, const TAB sc, const GTAB
       // reaches every Gaussian, visible or not
       const bool has_gs = sg.dL_dscales_out != nullptr;
       if (has_gs) {
+        float n[3] = {0.f, 0.f, 0.f};
+        if (!vis) noise_scale3<GEN>(sc.noise, nstream, i, n);
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
           if (!vis) {
-            const float n = sc.scale_noise ? sc.scale_noise[3 * i + k] : 0.f;
-            const ActScale a = act_scale(p_scale[3 * row + k], sc.scale_noise != nullptr, n);
-            dsc_draw[k] = scale_draw(a.act, a.pre, sc.scale_noise != nullptr, n);
+            const ActScale a = act_scale(p_scale[3 * row + k], noise_has_scale<GEN>(sc.noise), n[k]);
+            dsc_draw[k] = scale_draw(a.act, a.pre, noise_has_scale<GEN>(sc.noise), n[k]);
           }
           dscale[k] += sg.dL_dscales_out[3 * i + k] * dsc_draw[k];
         }
@@ -582,8 +597,7 @@ struct K8Views {
   const float* scales[GSR_MAX_BATCH_VIEWS];
   float* dL_dscales[GSR_MAX_BATCH_VIEWS];
   // scene input (raw leaves): per-view noise samples, per-view gradient arriving through the returned scales
-  const float* scale_noise[GSR_MAX_BATCH_VIEWS];
-  const float* sh_noise[GSR_MAX_BATCH_VIEWS];
+  NoiseViews noise;
   const float* dL_dscales_out[GSR_MAX_BATCH_VIEWS];
   // bit k set: view k's densification statistics count (the reference's trainers use the LAST view of a step only,
   // object_trainer.py:386-390; a caller sets the stat_* pointers on the GsrGrads entries of the views that count)
@@ -1082,7 +1096,7 @@ k_preprocess_bwd_views(const GsrView v, const GsrGaussians g, const K8Views vb, 
 
 // K8 over several views of a SCENE: the raw rows are read once, every view has its own (possibly noisy) scales, the
 // gradients of the raw leaves are summed over the views in registers and written once per model tensor.
-template <int KT>
+template <int KT, bool GEN = false>
 __global__ void __launch_bounds__(256)
 k_preprocess_bwd_views_scene(const GsrView v, const SceneTab sc, const SceneGradTab sg, const K8Views vb,
                              const GsrGrads out) {
@@ -1133,11 +1147,26 @@ k_preprocess_bwd_views_scene(const GsrView v, const SceneTab sc, const SceneGrad
     float gndx = 0.f, gndy = 0.f;
     // this view's scales and their derivative w.r.t. the raw (log) scaling
     float sa[3] = {0.f, 0.f, 0.f}, dsc[3] = {0.f, 0.f, 0.f};
+    // (the instantiations without the generator read the views' tensors as they always did: same registers as before)
+    [[maybe_unused]] NoiseSrc nsrc;
+    [[maybe_unused]] uint32_t nstream = 0u;
+    if constexpr (GEN) {
+      nsrc = vb.noise.view(vv);
+      nstream = noise_stream<GEN>(nsrc);
+    }
     if (ok && (vis || vb.dL_dscales_out[vv])) {
-      const float* sn = vb.scale_noise[vv];
+      [[maybe_unused]] const float* snt = vb.noise.scale[vv];
+      [[maybe_unused]] float nsc[3] = {0.f, 0.f, 0.f};
+      bool sn = snt != nullptr;
+      if constexpr (GEN) {
+        sn = noise_has_scale<GEN>(nsrc);
+        noise_scale3<GEN>(nsrc, nstream, i, nsc);
+      }
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
-        const float n = sn ? sn[3 * i + k] : 0.f;
+        float n;
+        if constexpr (GEN) n = nsc[k];
+        else n = snt ? snt[3 * i + k] : 0.f;
         const float pre = sn ? aact[k] + n * ((kSqrtPoint2 * aact[k]) / 4.0f) : aact[k];
         sa[k] = sn ? fmaxf(pre, 0.0f) : aact[k];
         dsc[k] = sn ? (pre >= 0.0f ? aact[k] * (1.0f + n * (kSqrtPoint2 / 4.0f)) : 0.0f) : aact[k];
@@ -1166,10 +1195,32 @@ k_preprocess_bwd_views_scene(const GsrView v, const SceneTab sc, const SceneGrad
         const float x = d.x, y = d.y, z = d.z, len = d.len;
         float b[16];
         sh_basis(D, x, y, z, b);
-        const float* nz = vb.sh_noise[vv] ? vb.sh_noise[vv] + (size_t)i * F : nullptr;
+        // (every normal is needed twice, on both sides of the clamp decision of the whole colour: GEN keeps them in registers)
+        [[maybe_unused]] const float* nzt = (!GEN && vb.noise.sh[vv]) ? vb.noise.sh[vv] + (size_t)i * F : nullptr;
+        bool nz = nzt != nullptr;
+        if constexpr (GEN) nz = noise_has_sh<GEN>(nsrc);
+        [[maybe_unused]] float nzr[GEN ? F : 1];
         float shv[F];
+        if constexpr (GEN) {
+          if (nz) {
 #pragma unroll
-        for (int k = 0; k < F; ++k) shv[k] = nz ? sh[k] + nz[k] * (kSqrtPoint2 * sh[k]) : sh[k];
+            for (int j = 0; j < (F + 3) / 4; ++j) {
+              float n4[4];
+              noise_sh4<GEN>(nsrc, nstream, i, j, F, n4);
+#pragma unroll
+              for (int e = 0; e < 4; ++e)
+                if (4 * j + e < F) nzr[4 * j + e] = n4[e];
+            }
+          } else {
+#pragma unroll
+            for (int k = 0; k < F; ++k) nzr[k] = 0.f;
+          }
+#pragma unroll
+          for (int k = 0; k < F; ++k) shv[k] = nz ? sh[k] + nzr[k] * (kSqrtPoint2 * sh[k]) : sh[k];
+        } else {
+#pragma unroll
+          for (int k = 0; k < F; ++k) shv[k] = nzt ? sh[k] + nzt[k] * (kSqrtPoint2 * sh[k]) : sh[k];
+        }
         float acc[3];
         sh_colour_n<KT>(D, shv, b, acc);
         float gch[3];
@@ -1186,7 +1237,8 @@ k_preprocess_bwd_views_scene(const GsrView v, const SceneTab sc, const SceneGrad
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
               const float gk = b[k] * gch[c];
-              dsh[3 * k + c] += nz ? gk * (1.0f + kSqrtPoint2 * nz[3 * k + c]) : gk;
+              if constexpr (GEN) dsh[3 * k + c] += nz ? gk * (1.0f + kSqrtPoint2 * nzr[3 * k + c]) : gk;
+              else dsh[3 * k + c] += nzt ? gk * (1.0f + kSqrtPoint2 * nzt[3 * k + c]) : gk;
             }
           }
         }
@@ -1374,8 +1426,10 @@ int gsr_launch_preprocess_bwd(int n_views, const GsrView* views, const GsrGaussi
       const uint32_t nbs = scene_tables(*g.scene, out.scene, t, gt);
       const size_t lds = gsr_preprocess_lds_bytes(v.sh_stride);
       return launch_sh<16, 9, 4, 1, 0>(fixed_sh(v.sh_stride), [&](auto kt) {
-        hipLaunchKernelGGL((k_preprocess_bwd<kt, true, SceneTab, SceneGradTab>), dim3(nbs), dim3(256), lds, stream, v, g,
-                           t, gt, geom.radii, out.partials, out);
+        with_flag(scene_noise_generated(1, &g), [&](auto gen) {
+          hipLaunchKernelGGL((k_preprocess_bwd<kt, true, SceneTab, SceneGradTab, gen>), dim3(nbs), dim3(256), lds, stream, v,
+                             g, t, gt, geom.radii, out.partials, out);
+        });
       });
     }
     const uint32_t nb = gsr_num_blocks(v.P);
@@ -1414,7 +1468,9 @@ int gsr_launch_preprocess_bwd(int n_views, const GsrView* views, const GsrGaussi
     SceneTab t; SceneGradTab gt;
     const uint32_t nbs = scene_tables(*g.scene, outs[0].scene, t, gt);
     return launch_sh<16, 9, 4, 1>(v.sh_stride, [&](auto kt) {
-      hipLaunchKernelGGL(k_preprocess_bwd_views_scene<kt>, dim3(nbs), dim3(256), lds, stream, v, t, gt, vb, out0);
+      with_flag(scene_noise_generated(n_views, gs), [&](auto gen) {
+        hipLaunchKernelGGL((k_preprocess_bwd_views_scene<kt, gen>), dim3(nbs), dim3(256), lds, stream, v, t, gt, vb, out0);
+      });
     });
   }
   if (plan.form == K8Form::kSparseViews) {

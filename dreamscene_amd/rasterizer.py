@@ -222,6 +222,25 @@ def _wait_pair_counts(words, n: int, event) -> None:
             time.sleep(0)            # let other Python threads (data loaders, other ranks' helper threads) take the GIL
 
 
+def _bind_noise(sc_struct, noise, scale_noise, sh_noise, dev):
+    """GsrScene's seeded-noise fields from a scene.NoiseSpec (or None). Returns the spec's stream tensor (or None): K8 reads it
+    again, so the state keeps it alive and the backward checks its version."""
+    if noise is None:
+        return None
+    if (noise.scales and scale_noise is not None) or (noise.shs and sh_noise is not None):
+        raise ValueError("a noise comes from its tensor (scale_noise= / sh_noise=) or from the generator (noise=), not both")
+    sc_struct.noise_seed = int(noise.seed)
+    sc_struct.noise_flags = (L.GSR_NOISE_SCALES if noise.scales else 0) | (L.GSR_NOISE_SHS if noise.shs else 0)
+    if not isinstance(noise.stream, torch.Tensor):
+        sc_struct.noise_stream = int(noise.stream)
+        return None
+    t = noise.stream
+    if t.device != dev or t.dtype != torch.int32 or t.numel() != 1 or not t.is_contiguous():
+        raise ValueError("a tensor noise stream is an int32[1] on the models' device")
+    sc_struct.noise_stream_dev = t.data_ptr()
+    return t
+
+
 def rasterize_forward_raw(s: GaussianRasterizationSettings, means3D, opacities, shs, colors_precomp, scales,
                           rotations, cov3D_precomp, want_keys: bool = False, want_aux: bool = True,
                           mode: Optional[str] = None, scene: Optional[dict] = None,
@@ -266,8 +285,8 @@ def _forward_steps(s: GaussianRasterizationSettings, means3D, opacities, shs, co
     event=<Event>) it allocates and binds, YIELDS (view struct, geom struct) for the caller to run
     gsr_forward_project_batch / gsr_forward_render_batch over all views, and continues when resumed.
     scene: {"models": [(xyz, scaling, rotation, opacity, features_dc, features_rest), ...] raw
-    leaf tensors, "scale_noise": [P,3] | None, "sh_noise": [P,K,3] | None, "want_act": bool}; the per-Gaussian
-    tensor arguments must then be None."""
+    leaf tensors, "scale_noise": [P,3] | None, "sh_noise": [P,K,3] | None, "noise": scene.NoiseSpec | None (the noises the
+    generator supplies), "want_act": bool}; the per-Gaussian tensor arguments must then be None."""
     lib = L.load()
     dev = (scene["models"][0][0] if scene is not None else means3D).device
     if dev.type != "cuda":
@@ -305,13 +324,14 @@ def _forward_steps(s: GaussianRasterizationSettings, means3D, opacities, shs, co
         if hn is not None and tuple(hn.shape) != (P, K_scene, 3):
             raise ValueError(f"sh_noise must be [P,K,3], got {tuple(hn.shape)}")
         sc_struct.scale_noise, sc_struct.sh_noise = _ptr(sn), _ptr(hn)
+        nstream = _bind_noise(sc_struct, scene.get("noise"), sn, hn, dev)
         sc_out["scales"] = torch.empty((P, 3), dtype=torch.float32, device=dev)
         sc_struct.scales_out = sc_out["scales"].data_ptr()
         if scene.get("want_act"):
             sc_out["rotations"] = torch.empty((P, 4), dtype=torch.float32, device=dev)
             sc_out["opacities"] = torch.empty((P,), dtype=torch.float32, device=dev)
             sc_struct.rotations_out, sc_struct.opacities_out = sc_out["rotations"].data_ptr(), sc_out["opacities"].data_ptr()
-        sc_keep.append((sn, hn))
+        sc_keep.append((sn, hn, nstream))
     else:
         P = int(means3D.shape[0])
     means3D = _prep(means3D, "means3D", dev)
@@ -541,8 +561,8 @@ def _forward_steps(s: GaussianRasterizationSettings, means3D, opacities, shs, co
                 ("scales", scales), ("rotations", rotations), ("cov3D_precomp", cov3D_precomp), ("bg", bg),
                 ("viewmatrix", vm), ("projmatrix", pm), ("campos", cp), ("rendered image", color_alias),
                 ("depth_alpha", da_alias)] +
-           ([(f"model {m} leaf {j}", t) for m, row in enumerate(sc_keep[:-1]) for j, t in enumerate(row)]
-            if sc_keep is not None else []))
+           ([(f"model {m} leaf {j}", t) for m, row in enumerate(sc_keep[:-1]) for j, t in enumerate(row)] +
+            [("noise stream", sc_keep[-1][2])] if sc_keep is not None else []))
     # ^ backward re-reads the output image (suffix sums from checkpoints). DETACHED aliases on purpose: the objects
     #   returned to autograd acquire grad_fn -> ctx -> this state; keeping them here would close a reference cycle
     #   and defer every free to Python's cyclic GC (measured: memory bloat and 5x slowdown after ~500 views).

@@ -95,7 +95,19 @@ typedef struct GsrScene {
   float* scales_out;           /* NULL or [P,3]: the activated (and augmented) scales scene_render returns (:892) */
   float* rotations_out;        /* NULL or [P,4]: normalised quaternions (parity tests)                        */
   float* opacities_out;        /* NULL or [P]:   sigmoid(opacity)        (parity tests)                        */
+  /* Seeded noise (SEMANTICS.md "Seeded noise"): the samples a tensor above would hold are computed inside K1 and again inside
+   * K8 as a pure function of (noise_seed, stream, concatenated Gaussian index, element) -- no tensor exists. All zero: today's
+   * meaning. A flag together with ITS tensor pointer, or an unknown flag bit, is GSR_EINVAL before any launch; one flag
+   * together with the other noise's tensor is legal. The views of a batched call share one K1 / K8 pass when the scenes that
+   * set flags agree on noise_seed and their noise_stream_dev, if given, are consecutive words (view k + 1 reads the word after
+   * view k's); otherwise K1 / K8 run view by view, with the same results. */
+  uint64_t noise_seed;
+  const uint32_t* noise_stream_dev; /* NULL, or device u32[1] read when the kernels run (forward AND backward) */
+  uint32_t noise_stream;            /* used when noise_stream_dev is NULL */
+  uint32_t noise_flags;             /* GSR_NOISE_*: that noise comes from the generator */
 } GsrScene;
+#define GSR_NOISE_SCALES 1u
+#define GSR_NOISE_SHS    2u
 /* Gradients w.r.t. the RAW leaf tensors of each model (same shapes). NULL entries are skipped. */
 typedef struct GsrModelGrads {
   float *xyz, *scaling, *rotation, *opacity, *features_dc, *features_rest;
@@ -562,6 +574,15 @@ int gsr_densify_plan(const GsrDensifyPlan* plan, void* scratch, size_t scratch_b
 int gsr_densify_plan_mask(const uint8_t* mask, int32_t P, void* scratch, size_t scratch_bytes, int32_t* sizes_dev,
                           int32_t* sizes_host, void* stream);
 int gsr_densify_apply(const GsrDensifyTable* table, const void* scratch, size_t scratch_bytes, int32_t* src, void* stream);
+
+/* ---- seeded noise as tensors (SEMANTICS.md "Seeded noise") -----------------------------------------------------------------------
+ * Writes the N(0,1) samples that GsrScene.noise_seed / noise_stream(_dev) / noise_flags stand for: scale_noise [P,3] and / or
+ * sh_noise [P,K,3] (either may be NULL) of the Gaussians 0..P-1 of the concatenated index space. A scene given these tensors
+ * renders, and differentiates, bit for bit like the same scene with the flags set. stream_dev: NULL, or a device u32[1] read
+ * when the kernel runs (then `stream` is ignored). One launch on `hip_stream`, no synchronisation, no allocation.
+ * Checked in this order, before any HIP call: P < 0, K outside 1..16, both outputs NULL -> GSR_EINVAL; P == 0 -> 0, no launch. */
+int gsr_noise_fill(uint64_t seed, uint32_t stream, const uint32_t* stream_dev, int32_t P, int32_t K, float* scale_noise,
+                   float* sh_noise, void* hip_stream);
 
 /* ---- object placement: SceneGaussian.add_objects_to_scene (scene_gaussian.py:318-427; dreamscene_amd/compose.py; SEMANTICS.md
  * "Object placement") ---------------------------------------------------------------------------------------------------------------
