@@ -211,6 +211,13 @@ int gsr_forward_project_batch(int32_t n_views, const GsrView* views, const GsrGa
   if (n_views < 1 || n_views > GSR_MAX_BATCH_VIEWS || !views || !gs || !geoms || !n_pairs_pinned) return GSR_EINVAL;
   const GsrGaussians* g = &gs[0];
   const GsrView& v0 = views[0];
+  // several views share launches on the column path only (gsrast.h: image at most 4096 x 4096, P < 2^24): rejected here, with
+  // the other argument checks -- before a count word is written or anything is enqueued
+  if (n_views > 1) {
+    const int rc = check_view(&v0);
+    if (rc) return rc;
+    if (!gsr_uses_columns(v0)) return GSR_EINVAL;
+  }
   size_t bstride = 0;
   for (int k = 0; k < n_views; ++k) {
     int rc = check_view(&views[k]);
@@ -250,9 +257,14 @@ int gsr_forward_project_batch(int32_t n_views, const GsrView* views, const GsrGa
       }
     }
   }
-  // k_col_plan stores the views' counts straight into the caller's page-locked array (no copy operation)
-  int rc = gsr_launch_depth_order(geoms[0], v0, stream, prof, n_views, bstride, n_pairs_pinned, /*early=*/false);
+  // k_col_plan stores the views' counts straight into the caller's page-locked array (no copy operation); one view on a
+  // larger grid (no k_col_plan there) gets its count by the copy forward_project uses on that path, so the word never stays pending
+  const bool direct = gsr_uses_columns(v0);
+  int rc = gsr_launch_depth_order(geoms[0], v0, stream, prof, n_views, bstride, direct ? n_pairs_pinned : nullptr,
+                                  /*early=*/false);
   if (rc) return rc;
+  if (!direct)
+    GSR_HIP(hipMemcpyAsync(n_pairs_pinned, gsr_pair_counts(geoms[0], v0.P), sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
   for (int k = 1; k < n_views; ++k)
     geoms[k].sorted_idx = reinterpret_cast<uint32_t*>((char*)geoms[0].sorted_idx + (size_t)k * bstride);
   return GSR_OK;

@@ -132,9 +132,9 @@ def eligible(s, means3D, means2D, opacities, shs, colors_precomp, scales, rotati
     if context is not None and (context.grad_arena is not None or context.profile is not None or
                                 context.densify_stats is not None or context.forward_mode != "auto"):
         return False
-    if means3D.device.type != "cuda" or means3D.shape[0] == 0 or means3D.shape[0] >= (1 << 24):
+    if means3D.device.type != "cuda" or means3D.shape[0] == 0:
         return False
-    if (int(s.image_width) + 15) // 16 > 256 or (int(s.image_height) + 15) // 16 > 256:
+    if not R.uses_columns(means3D.shape[0], s.image_height, s.image_width):
         return False
     if scales.dim() != 2 or shs.dim() != 3 or shs.shape[1] not in (1, 4, 9, 16):
         return False

@@ -182,6 +182,11 @@ class CapturedViews(torch.nn.Module):
         for t in persistent + ((scales,) if per_view else ()):
             if t.dtype != torch.float32 or not t.is_contiguous():
                 raise ValueError("CapturedViews inputs must be contiguous fp32 tensors")
+        s0 = settings_list[0]
+        if not R.uses_columns(means3D.shape[0], s0.image_height, s0.image_width):
+            # grids beyond 256 tiles a side (or P >= 2^24): the library bins them on its general path, which shares no launches
+            # between views (gsr_forward_project_batch rejects V > 1) -- nothing to capture, and no warm-up to count
+            return self._eager_forward(settings_list, means3D, opacities, shs, scales, rotations, rc)
         # A capture reads the caller's parameter tensors IN PLACE (persistent leaves, updated in place by the optimizer:
         # nothing is copied) and is therefore keyed on their addresses. Callers that hand over fresh tensors every step
         # -- the reference's trainers pass activations: get_features is a torch.cat, get_opacity a sigmoid, get_scaling an

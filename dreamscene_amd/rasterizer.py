@@ -254,6 +254,13 @@ def rasterize_forward_raw(s: GaussianRasterizationSettings, means3D, opacities, 
     raise RuntimeError("unreachable: a non-batched forward does not yield")
 
 
+def uses_columns(P: int, H: int, W: int) -> bool:
+    """Does libgsrast bin this view on its column path (binning.hip use_columns: at most 256 x 256 tiles and P < 2^24)? Only
+    that path takes several views through shared launches and stores the pair count from a kernel, so the batched forward
+    (views.py), the captured one (graph.py) and the drop-in ring (dropin.py) are for such views; the others go one by one."""
+    return (int(W) + 15) // 16 <= 256 and (int(H) + 15) // 16 <= 256 and int(P) < (1 << 24)
+
+
 # GsrBinning.seg_len (include/gsrast.h): list entries per forward checkpoint = per work item of the backward. A backward item
 # is a serial recurrence over its entries (~0.3 us each on MI355X), so no launch ends before its longest item has: 65-90 us
 # with 256 entries, whatever the size of the launch. Launches with little total work (one view of the reference's per-view

@@ -67,7 +67,7 @@ def rasterize_views_forward_raw(settings_list: Sequence, means3D, opacities, shs
         raise ValueError("score_sum with score_mode 0: use views.importance_scores (it sums raw pixel counts, score_mode 2, "
                          "and applies the opacity once)")
     batched = (1 < V <= MAX_VIEWS and same and P > 0 and rc.forward_mode == "auto" and ws.hint.get((P, H, W)) is not None
-               and (W + 15) // 16 <= 256 and (H + 15) // 16 <= 256 and P < (1 << 24))
+               and R.uses_columns(P, H, W))
 
     # one segment length for all views of the call (their backward is one launch): from the capacity the batch will use --
     # or, before any capacity is known, whatever the first view picks for its exact size
@@ -168,7 +168,7 @@ def _views_forward_scene(lib, settings_list, scenes, want_aux, rc):
     ws = R._workspace(dev, stream)
     K = 1 + (int(models[0][5].shape[1]) if models[0][5] is not None and models[0][5].numel() > 0 else 0)
     batched = (1 < V <= MAX_VIEWS and same and P > 0 and rc.forward_mode == "auto" and ws.hint.get((P, H, W)) is not None
-               and (W + 15) // 16 <= 256 and (H + 15) // 16 <= 256 and P < (1 << 24) and K in (1, 4, 9, 16)
+               and R.uses_columns(P, H, W) and K in (1, 4, 9, 16)
                and not any(s.score_flag for s in settings_list))
     seg = rc.seg_len or (R.pick_seg_len(int(ws.hint[(P, H, W)] * 1.5), V) if ws.hint.get((P, H, W)) else None)   # one per call
     if not batched:

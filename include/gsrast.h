@@ -325,8 +325,11 @@ int gsr_forward_project_async(const GsrView*, const GsrGaussians*, GsrGeom*, uin
 
 /* The same for n_views views of the SAME Gaussians (the C_batch_size views of one optimizer step,
  * object_trainer.py:302-382): the launch-latency-bound depth sorts and column counts of all views go through each
- * launch together. Requirements: equal P / image size / sh_stride, image at most 4096 x 4096, and the views'
- * GsrGeom.scratch buffers equally spaced (geoms[k].scratch == geoms[0].scratch + k * stride, stride a multiple of 256).
+ * launch together. Requirements: equal P / image size / sh_stride, and the views' GsrGeom.scratch buffers equally
+ * spaced (geoms[k].scratch == geoms[0].scratch + k * stride, stride a multiple of 256). n_views > 1 also requires a grid
+ * of at most 256 x 256 tiles (image at most 4096 x 4096) and P < 2^24: anything else is GSR_EINVAL from the argument
+ * checks, with nothing enqueued and n_pairs_pinned untouched (render such views one by one). n_views == 1 accepts any
+ * size; beyond those limits its count arrives by a device-to-host copy enqueued behind the projection.
  * gaussians[k] are the inputs of view k: identical pointers for every view except `scales`, which may be a different
  * tensor per view (the trainers add fresh noise to the activated scales of every view, scene_gaussian.py:1004-1008);
  * with a `scene`, every view has its own GsrScene holding the SAME models and its own noise samples / scales_out.

@@ -65,6 +65,50 @@ def test_pure_helpers_without_gpu(built_lib):
     assert lib.gsr_backward(None, None, None, None, None, None, None, None, None) == -1
 
 
+def test_project_batch_rejects_several_views_beyond_256_tiles_before_touching_anything(built_lib):
+    """gsr_forward_project_batch, n_views = 2, a 40 x 4100 view (257 tile columns: the general binning path, which shares no
+    launches between views): GSR_EINVAL from the argument checks -- the caller's count words are as it left them and nothing
+    was enqueued. Every OTHER argument is valid (aligned, non-NULL, equally spaced scratch buffers of the size the library
+    asks for), so only the grid can be what it objects to; the buffers are host memory and the stream is a made-up handle,
+    which a library that went on to K1 could not survive quietly: before the check moved in front of K1 this call zeroed the
+    words, armed them with GSR_N_PENDING and launched."""
+    import numpy as np
+    from dreamscene_amd import _lib
+    lib = built_lib
+    P, K, V = 300, 4, 2
+    sb = int(lib.gsr_project_scratch_bytes(P))
+    stride = (sb + 255) // 256 * 256
+    sizes = dict(means3D=P * 12, opacities=P * 4, shs=P * K * 12, scales=P * 12, rotations=P * 16, cam=64 * 4,
+                 splat=V * P * 48, radii=V * P * 4, tiles=V * P * 4, offs=V * (int(lib.gsr_num_blocks(P)) + 8) * 4,
+                 scratch=V * stride)
+    arena = np.zeros(sum((n + 255) // 256 * 256 for n in sizes.values()) + 256, np.uint8)
+    at, ptr = (arena.ctypes.data + 255) // 256 * 256, {}
+    for name, n in sizes.items():
+        ptr[name] = at
+        at += (n + 255) // 256 * 256
+    views = (_lib.GsrView * V)()
+    gauss = (_lib.GsrGaussians * V)()
+    geoms = (_lib.GsrGeom * V)()
+    for k in range(V):
+        v = views[k]
+        v.P, v.sh_stride, v.sh_degree, v.image_height, v.image_width = P, K, 1, 40, 4100
+        v.tanfovx, v.tanfovy, v.scale_modifier = 2.3, 0.022, 1.0
+        v.bg, v.viewmatrix, v.projmatrix, v.campos = ptr["cam"], ptr["cam"] + 16, ptr["cam"] + 80, ptr["cam"] + 144
+        g = gauss[k]
+        g.means3D, g.opacities, g.shs, g.scales, g.rotations = (ptr[n] for n in ("means3D", "opacities", "shs", "scales",
+                                                                                 "rotations"))
+        ge = geoms[k]
+        ge.splat, ge.radii, ge.tiles_touched = ptr["splat"] + k * P * 48, ptr["radii"] + k * P * 4, ptr["tiles"] + k * P * 4
+        ge.block_offsets = ptr["offs"] + k * (int(lib.gsr_num_blocks(P)) + 8) * 4
+        ge.scratch, ge.scratch_bytes = ptr["scratch"] + k * stride, sb
+    words = (ctypes.c_uint64 * V)(0x1234, 0x5678)
+    made_up_stream = ctypes.c_void_p(0x10)
+    rc = lib.gsr_forward_project_batch(V, views, gauss, geoms, ctypes.addressof(words), made_up_stream, None)
+    assert rc == -1, rc                                            # GSR_EINVAL
+    assert list(words) == [0x1234, 0x5678], [hex(w) for w in words]
+    assert geoms[0].sorted_idx is None and geoms[1].sorted_idx is None
+
+
 def test_struct_layouts_match_header(built_lib):
     """ctypes mirrors of the POD structs have the sizes the C compiler gives them."""
     from dreamscene_amd import _lib

@@ -109,6 +109,37 @@ def test_random_cameras_and_scale_modifier_c_vs_float64(c_oracle, seed):
         assert e <= 1e-5, (tk, e)
 
 
+# float64 is no arbiter for SMALL splats on these images, whatever the seed: a pixel coordinate near 4096 has an fp32 ulp of
+# 2.4e-4 px, and a splat of sigma s px turns a coordinate error d into a relative alpha error of ~3 d / s -- 1e-3 at one
+# pixel, and measured so (scale factor 1, seeds 1-8 of either camera: image 2e-6 ... 1.7e-3, integer artefacts differing on
+# half of the seeds: a gate taken the other way). That rounding is part of the fp32 definition the device shares with the C
+# oracle operation by operation (tests/test_wide_grids.py compares the pixel centres bit for bit). What THIS test is about
+# is the camera -- the projection, its Jacobian and their gradients at tan(fov / 2) = 2.3 x 0.02 -- so it renders the cases'
+# scenes with every scale times 5 (sigma ~100 px), where coordinate rounding is below this file's bars; the cases' own
+# seeds pass there, none had to be replaced.
+STRIP_SCALE_MUL = 5.0
+
+
+@pytest.mark.parametrize("case", ["wide", "tall"])
+def test_strip_cameras_c_vs_float64(c_oracle, case):
+    """The cameras of tests/test_wide_grids.py (more than 256 tile columns / rows; the same focal length on both axes, so
+    tan(fov / 2) = 2.3 x 0.022 and 0.013 x 2.3) with P cut to 300 -- the float64 oracle is dense in pixels x Gaussians: the C
+    oracle that arbitrates 1e-5 on the GPU there is itself within this file's bars of float64 autograd, tile lists beyond
+    column / row 255 included."""
+    from tests.util import wide_grid_case
+    g, cam, bg, P, K, D = wide_grid_case(case, P=300, scale_mul=STRIP_SCALE_MUL)
+    f, rep = _c_vs_float64(c_oracle, g, cam, bg, P, K, D, 1.0, 3)
+    gx, gy = (cam.image_width + 15) // 16, (cam.image_height + 15) // 16
+    cnt = (f["ranges"][:, 1].astype(np.int64) - f["ranges"][:, 0]).reshape(gy, gx)
+    print(f"[strip {case}] visible {int((f['radii'] > 0).sum())}, N {f['N']}, entries beyond index 255: "
+          f"{int(cnt[:, 256:].sum() + cnt[256:].sum())}; " + " ".join(f"{k} {v:.1e}" for k, v in rep.items()))
+    assert int((f["radii"] > 0).sum()) >= 200 and cnt[:, 256:].sum() + cnt[256:].sum() > 0
+    assert rep.pop("image") <= 2e-6
+    assert rep.pop("depth_alpha") <= 2e-5
+    for tk, e in rep.items():
+        assert e <= 1e-5, (tk, e)
+
+
 def test_needles_vs_float64(c_oracle):
     """Needle-shaped, flat and zero-size splats (scale noise + clamp(.., 0), scene_gaussian.py:1005-1008): the scalar
     fp32 oracle against float64 autograd. The covariance gradient is accumulated per pixel as q (Sigma^-1 d)(Sigma^-1 d)^T

@@ -15,7 +15,78 @@ def small_scene(P=600, H=96, W=80, K=16, seed=3, scale_mul=6.0, radius=3.0, cam_
     return g, cam
 
 
-FUZZ_FOVS = (0.2, 0.46, 1.2, 2.2)          # tan(fov / 2) from 0.10 to 1.96: both sides of 1
+def strip_camera(H, W, focal_px, radius=3.0, theta=70.0, phi=30.0) -> Camera:
+    """An orbit camera with the SAME focal length in pixels on both axes, whatever the aspect. (synth.object_cameras derives
+    FoVy from the aspect the reference's way: at 16 x 4112 that is tanfovy = 60 and every splat covers the whole image.)"""
+    import math
+    from dreamscene_amd.camera import orbit_pose
+    return Camera.from_RT(*orbit_pose(radius, theta, phi), 2.0 * math.atan(W / (2.0 * focal_px)),
+                          2.0 * math.atan(H / (2.0 * focal_px)), H, W)
+
+
+WIDE_GRID_SCALE_FACTORS = (0.2, 0.6, 2.5)    # per-Gaussian footprints on both sides of 32 tiles (k_emit_pairs' two branches)
+
+
+def wide_grid_scene(P, K, seed, cam: Camera, stretch_x=1.0, stretch_y=1.0, scale_mul=1.0, core_frac=0.3):
+    """A seeded scene that USES a grid of more than 256 tiles a side: synth.g_object(P, seed, K) with
+      * each Gaussian's scales times one of WIDE_GRID_SCALE_FACTORS (times scale_mul),
+      * the means stretched along the camera's image axes: Gaussian i by 1 + (stretch - 1) u_i, u_i ~ U(0, 1) (the object is
+        a ball of radius 0.5; a 4100 px strip at focal length 890 px and distance 3 spans ~14 of them), so that splats land in
+        the last tile column / row (index 256, 4 px wide at 4100 px); a stretch below 1 squeezes every Gaussian alike (into the
+        40 or 24 px of a strip's short side),
+      * the last core_frac of the Gaussians not stretched but pulled to 0.15 of their distance from the centre: a few tiles
+        at the image centre hold hundreds of entries (several 256-entry batches, checkpoints),
+      * the first 5 % of the means moved far off (* 40): culled.
+    What a case must reach is asserted by its test from the C oracle's outputs (tests/test_wide_grids.py)."""
+    g = synth.g_object(P, seed=seed, K=K)
+    rng = np.random.default_rng(7000 + seed)
+    f = rng.choice(np.asarray(WIDE_GRID_SCALE_FACTORS, np.float32), size=(P, 1))
+    g["scales"] = (g["scales"] * f * np.float32(scale_mul)).astype(np.float32)
+    # rows of the W2C rotation = the camera's axes in world coordinates (world_view_transform is its transpose)
+    right = cam.world_view_transform[:3, 0].astype(np.float64)
+    down = cam.world_view_transform[:3, 1].astype(np.float64)
+    m = g["means3D"].astype(np.float64)
+    u = rng.uniform(size=(P, 1))
+    core = slice(P - int(P * core_frac), P)
+    u[core] = 0.0
+    m[core] *= 0.15
+    fx = 1.0 + (stretch_x - 1.0) * (u if stretch_x > 1.0 else 1.0)
+    fy = 1.0 + (stretch_y - 1.0) * (u if stretch_y > 1.0 else 1.0)
+    m = m + (fx - 1.0) * (m @ right)[:, None] * right + (fy - 1.0) * (m @ down)[:, None] * down
+    m[:max(1, P // 20)] *= 40.0
+    g["means3D"] = np.ascontiguousarray(m, dtype=np.float32)
+    return g
+
+
+# The smallest shapes that reach each branch of the general binning path (more than 256 tile columns or rows):
+#   wide    257 x 3 tiles, ragged on both axes: 9 tile bits, two sort passes, the last pass lands in point_list
+#   tall    2 x 257 tiles: gy > 256, narrow gx
+#   square  257 x 257 = 66 049 tiles: 17 tile bits, three passes, the ping-pong buffers the other way round, tile ids > 65 535
+#   many    gsr_num_blocks(263 000) = 1028 > 1024: the second trip of k_scan_blocks' loop; a tile list thousands deep
+WIDE_GRID_FOCAL = 890.0      # px: tan(fov / 2) = 2.3 along 4100 px, 0.022 / 0.013 along 40 / 24 px
+WIDE_GRID_CASES = dict(
+    wide=dict(H=40, W=4100, P=1500, K=16, D=3, seed=1, stretch_x=20.0, stretch_y=0.15),
+    tall=dict(H=4100, W=24, P=1500, K=4, D=1, seed=2, stretch_x=0.15, stretch_y=20.0),
+    square=dict(H=4100, W=4112, P=1200, K=16, D=3, seed=3, stretch_x=20.0, stretch_y=20.0),
+    many=dict(H=24, W=4100, P=263_000, K=1, D=0, seed=4, stretch_x=20.0, stretch_y=0.15, scale_mul=0.5, core_frac=0.02),
+)
+
+
+def wide_grid_case(name, P=None, phi=30.0, scale_mul=None, seed=None):
+    """-> (g, cam, bg, P, K, D) of a WIDE_GRID_CASES entry (P, the camera's azimuth and the scale factor may be overridden)."""
+    c = dict(WIDE_GRID_CASES[name])
+    H, W, K, D, c_seed = (c.pop(k) for k in ("H", "W", "K", "D", "seed"))
+    seed = c_seed if seed is None else seed
+    P = int(P or c.pop("P"))
+    c.pop("P", None)
+    if scale_mul is not None:
+        c["scale_mul"] = c.get("scale_mul", 1.0) * scale_mul
+    cam = strip_camera(H, W, WIDE_GRID_FOCAL, phi=phi)
+    g = wide_grid_scene(P, K, seed, cam, **c)
+    return g, cam, np.array([0.2, 0.7, 1.0], np.float32), P, K, D
+
+
+FUZZ_FOVS = (0.2, 0.46, 1.2, 2.2)         # tan(fov / 2) from 0.10 to 1.96: both sides of 1
 FUZZ_RADII = (0.6, 1.5, 3.0, 6.0)         # 0.6: the eye at the rim of the cloud (near-plane culls, huge footprints)
 FUZZ_SCALE_MODIFIERS = (0.25, 0.5, 1.0, 1.7, 3.0)
 
