@@ -189,6 +189,8 @@ SYMBOLS = [
     ("gsr_forward_project_batch", C.c_int, [C.c_int32, C.POINTER(GsrView), C.POINTER(GsrGaussians), C.POINTER(GsrGeom),
                                             C.c_void_p, C.c_void_p, C.c_void_p]),
     ("gsr_pack_views", C.c_int, [C.c_int32, C.POINTER(GsrView), C.c_void_p, C.c_void_p]),
+    ("gsr_pack_views_streams", C.c_int, [C.c_int32, C.POINTER(GsrView), C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
     ("gsr_forward_render", C.c_int, [C.POINTER(GsrView), C.POINTER(GsrGeom), C.c_uint64, C.POINTER(GsrBinning),
                                      C.POINTER(GsrImages), C.c_void_p, C.c_void_p]),
     ("gsr_backward_views", C.c_int, [C.c_int32, C.POINTER(GsrView), C.POINTER(GsrGaussians), C.POINTER(GsrGeom),

@@ -138,9 +138,12 @@ struct PackViews {
   const float* projmatrix[GSR_MAX_BATCH_VIEWS];
   const float* campos[GSR_MAX_BATCH_VIEWS];
   float tanfovx[GSR_MAX_BATCH_VIEWS], tanfovy[GSR_MAX_BATCH_VIEWS], sh_degree[GSR_MAX_BATCH_VIEWS];
+  uint32_t streams[GSR_MAX_BATCH_VIEWS];   // gsr_pack_views_streams: the views' noise stream ids, by value
 };
-// one workgroup per view, one thread per float of the packed row
-__global__ void __launch_bounds__(64) k_pack_views(const PackViews pv, float* __restrict__ packed) {
+// one workgroup per view, one thread per float of the packed row; the last lane stores the view's stream word (streams_dev
+// NULL: gsr_pack_views, nothing stored)
+__global__ void __launch_bounds__(64) k_pack_views(const PackViews pv, float* __restrict__ packed,
+                                                   uint32_t* __restrict__ streams_dev) {
   const int k = blockIdx.x, t = threadIdx.x;
   float x = 0.f;
   if (t < 3) x = pv.bg[k][t];
@@ -151,10 +154,12 @@ __global__ void __launch_bounds__(64) k_pack_views(const PackViews pv, float* __
   else if (t == 41) x = pv.tanfovy[k];
   else if (t == 42) x = pv.sh_degree[k];
   if (t < GSR_PACKED_VIEW_FLOATS) packed[k * GSR_PACKED_VIEW_FLOATS + t] = x;
+  if (streams_dev && t == 63) streams_dev[k] = pv.streams[k];
 }
 }  // namespace
 
-int gsr_pack_views(int32_t n_views, const GsrView* views, float* packed, void* stream_) {
+int gsr_pack_views_streams(int32_t n_views, const GsrView* views, const uint32_t* streams, float* packed,
+                           uint32_t* streams_dev, void* stream_) {
   if (n_views < 1 || n_views > GSR_MAX_BATCH_VIEWS || !views || !packed || !aligned16(packed)) return GSR_EINVAL;
   PackViews pv = PackViews{};
   for (int k = 0; k < n_views; ++k) {
@@ -166,10 +171,18 @@ int gsr_pack_views(int32_t n_views, const GsrView* views, float* packed, void* s
     pv.campos[k] = views[k].campos;
     pv.tanfovx[k] = views[k].tanfovx; pv.tanfovy[k] = views[k].tanfovy; pv.sh_degree[k] = (float)views[k].sh_degree;
   }
+  if (!streams || !streams_dev) streams_dev = nullptr;      // either one missing: exactly gsr_pack_views
+  if (streams_dev && (reinterpret_cast<uintptr_t>(streams_dev) & 3u)) return GSR_EINVAL;
+  if (streams_dev)
+    for (int k = 0; k < n_views; ++k) pv.streams[k] = streams[k];
   GsrDeviceGuard dev(packed);
-  hipLaunchKernelGGL(k_pack_views, dim3((uint32_t)n_views), dim3(64), 0, (hipStream_t)stream_, pv, packed);
+  hipLaunchKernelGGL(k_pack_views, dim3((uint32_t)n_views), dim3(64), 0, (hipStream_t)stream_, pv, packed, streams_dev);
   GSR_HIP(hipGetLastError());
   return GSR_OK;
+}
+
+int gsr_pack_views(int32_t n_views, const GsrView* views, float* packed, void* stream_) {
+  return gsr_pack_views_streams(n_views, views, nullptr, packed, nullptr, stream_);
 }
 
 static int forward_project(const GsrView* v, const GsrGaussians* g, GsrGeom* geom, uint64_t* n_pairs_host,

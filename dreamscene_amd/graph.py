@@ -75,6 +75,40 @@ class _Pending:
         self.done = False
 
 
+def user_view(s, P, K, rc):
+    """The GsrView of the step's settings `s` as gsr_pack_views reads it (shared with scene_graph.py)."""
+    if (int(s.sh_degree) + 1) ** 2 > K:     # the eager path answers GSR_EINVAL; a replay must not clamp silently
+        raise ValueError(f"sh_degree {int(s.sh_degree)} needs {(int(s.sh_degree) + 1) ** 2} SH coefficients, shs holds {K}")
+    dev = s.viewmatrix.device
+    f = lambda t, n: R._prep(t.reshape(-1), n, dev, align=4)
+    bg, vm, pm, cp = f(s.bg, "bg"), f(s.viewmatrix, "viewmatrix"), f(s.projmatrix, "projmatrix"), f(s.campos, "campos")
+    v = R._view_struct(s, P, K, bg, vm, pm, cp, rc.score_mode)
+    v._keep = (bg, vm, pm, cp)          # until gsr_pack_views has been enqueued (stream order covers the rest)
+    return v
+
+
+def poll_pair_counts(pinned_np, V: int, event, host_stats=None) -> None:
+    """Blocks until the first V pinned pair-count words of a replayed forward graph hold counts (armed with -1 before the
+    replay), or `event` -- recorded behind the graph -- has completed."""
+    t_wait = time.perf_counter()
+    spins = 0
+    while True:
+        if int(pinned_np[:V].min()) >= 0:
+            break
+        spins += 1
+        if (spins & 63) == 0 and event.query():
+            break
+    if host_stats is not None:
+        host_stats.wait_s += time.perf_counter() - t_wait
+
+
+def capacity_for(peak_n: int, headroom: float) -> int:
+    """The pair capacity of a capture: headroom x the largest count seen, on the eager path's coarse grid (1/8 octave)."""
+    want = int(peak_n * headroom) + 65536
+    q = max(65536, 1 << max(0, want.bit_length() - 4))
+    return (want + q - 1) // q * q
+
+
 class _CapturedFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, shs, opacities, scales, rotations, owner, settings_list, rc, differentiable):
@@ -239,17 +273,7 @@ class CapturedViews(torch.nn.Module):
             # third of the way into graph F. The host polls them (page-locked, device-visible memory: nothing else tells the
             # host that a kernel INSIDE a graph has finished) so that the capacity check is over while the compositing
             # still runs; if the words only become visible when the graph is done, the event ends the wait.
-            t_wait = time.perf_counter()
-            spins = 0
-            while True:
-                ns = cap.pinned_np[:V]
-                if int(ns.min()) >= 0:
-                    break
-                spins += 1
-                if (spins & 63) == 0 and cap.evF.query():
-                    break
-            if rc.host_stats is not None:
-                rc.host_stats.wait_s += time.perf_counter() - t_wait
+            poll_pair_counts(cap.pinned_np, V, cap.evF, rc.host_stats)
         ns = [int(x) for x in cap.pinned_np[:V]]
         self._peak_n = max([self._peak_n] + ns)
         self.stats["replays"] += 1
@@ -261,14 +285,7 @@ class CapturedViews(torch.nn.Module):
         return cap.outs, cap, None
 
     def _user_view(self, s, P, K, rc):
-        if (int(s.sh_degree) + 1) ** 2 > K:     # the eager path answers GSR_EINVAL; a replay must not clamp silently
-            raise ValueError(f"sh_degree {int(s.sh_degree)} needs {(int(s.sh_degree) + 1) ** 2} SH coefficients, shs holds {K}")
-        dev = s.viewmatrix.device
-        f = lambda t, n: R._prep(t.reshape(-1), n, dev, align=4)
-        bg, vm, pm, cp = f(s.bg, "bg"), f(s.viewmatrix, "viewmatrix"), f(s.projmatrix, "projmatrix"), f(s.campos, "campos")
-        v = R._view_struct(s, P, K, bg, vm, pm, cp, rc.score_mode)
-        v._keep = (bg, vm, pm, cp)          # until gsr_pack_views has been enqueued (stream order covers the rest)
-        return v
+        return user_view(s, P, K, rc)
 
     def _capture(self, sig, settings_list, means3D, opacities, shs, scales, rotations, rc, per_view) -> _Captured:
         lib = L.load()
@@ -278,9 +295,7 @@ class CapturedViews(torch.nn.Module):
         P, K, H, W = int(means3D.shape[0]), int(shs.shape[1]), int(s0.image_height), int(s0.image_width)
         cap = _Captured()
         cap.sig, cap.P, cap.K, cap.V = sig, P, K, V
-        want = int(self._peak_n * self.headroom) + 65536
-        q = max(65536, 1 << max(0, want.bit_length() - 4))
-        cap.cap = (want + q - 1) // q * q
+        cap.cap = capacity_for(self._peak_n, self.headroom)
         f32 = torch.float32
         with torch.cuda.device(dev):
             cap.packed = torch.zeros((V, L.GSR_PACKED_VIEW_FLOATS), dtype=f32, device=dev)

@@ -934,11 +934,16 @@ def rasterize_backward_raw(st: _State, dL_dcolor, dL_ddepth_alpha, cam_grads: bo
 
 
 def rasterize_backward_views_scene_raw(states, dL_dcolors, dL_ddepth_alphas, model_grads=None, accumulate: bool = False,
-                                       dL_dscales_outs=None, stats=None, stats_views=None, profile=None) -> dict:
+                                       dL_dscales_outs=None, stats=None, stats_views=None, profile=None,
+                                       reuse: Optional[dict] = None, private_scratch: bool = False) -> dict:
     """Backward of several views of the same SCENE (raw leaves, rasterize_forward_raw(scene=...) per view or batched):
     K7 per view, one K8 pass over all views; the gradients of the raw leaves are the sums over the views, written to (or,
     with accumulate, added to) one tensor per leaf. dL_dscales_outs: per view, the gradient arriving through the returned
-    scales (or None). stats / stats_views: see RasterContext."""
+    scales (or None). stats / stats_views: see RasterContext.
+    reuse: the dict a previous call with the same arguments returned -- its per-view means2D rows and its scratch receive the
+    results again and nothing is allocated (graph capture, scene_graph.py; the caller passes the dict's `model_grads` back as
+    model_grads when they are not its own buffers). private_scratch: a K7 -> K8 scratch of the call's own instead of the cached
+    one eager calls on the stream share (a captured graph keeps its scratch: a replay does not pass through here)."""
     V = len(states)
     st0 = states[0]
     dev, P, K = st0.dev, st0.P, st0.K
@@ -946,8 +951,11 @@ def rasterize_backward_views_scene_raw(states, dL_dcolors, dL_ddepth_alphas, mod
         _check_versions(st)
     sc0, keep0 = st0.scene
     outs = _model_grad_rows(sc0, keep0, model_grads, accumulate, K, dev)
-    m2d = torch.empty((V, max(P, 1), 3), dtype=torch.float32, device=dev)
-    scratch = _scratch_acquire(dev, V, P)
+    if reuse is not None:
+        m2d, scratch = reuse["_m2d"], reuse["_scratch"]
+    else:
+        m2d = torch.empty((V, max(P, 1), 3), dtype=torch.float32, device=dev)
+        scratch = _scratch_acquire(dev, V, P, private=private_scratch)
     image_grads = [_prep_image_grads(dL_dcolors[k], dL_ddepth_alphas[k], dev) for k in range(V)]
     grs = (L.GsrGrads * V)()
     sgs = [L.GsrSceneGrads() for _ in range(V)]     # (one per view: each carries its own dL_dscales_out)
@@ -963,7 +971,7 @@ def rasterize_backward_views_scene_raw(states, dL_dcolors, dL_ddepth_alphas, mod
     for k in _stat_views(V, stats, stats_views):
         _bind_stats(grs[k], stats, P, dev)
     _enqueue_backward("gsr_backward_views", states, grs, image_grads, scratch, None, profile)
-    return dict(dL_dmeans2D=m2d[:, :P], model_grads=outs)
+    return dict(dL_dmeans2D=m2d[:, :P], model_grads=outs, _m2d=m2d, _scratch=scratch)
 
 
 def rasterize_backward_views_raw(states, dL_dcolors, dL_ddepth_alphas, arena=None, accumulate: bool = False,

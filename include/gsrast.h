@@ -352,6 +352,12 @@ int gsr_forward_project_batch(int32_t n_views, const GsrView* views, const GsrGa
  * aligned; no host synchronisation. */
 #define GSR_PACKED_VIEW_FLOATS 44
 int gsr_pack_views(int32_t n_views, const GsrView* views, float* packed, void* stream);
+/* The same launch also stores the views' noise stream ids: streams_dev[k] = streams[k] (streams: n_views HOST words, taken by
+ * value with the call; streams_dev: n_views device words, 4-byte aligned -- what the GsrScene.noise_stream_dev of a captured
+ * step's views point at, view k at word k). A caller that replays a captured scene step refreshes cameras and ids with this
+ * one call, at the forward only: K8 reads the words again. streams or streams_dev NULL: exactly gsr_pack_views. */
+int gsr_pack_views_streams(int32_t n_views, const GsrView* views, const uint32_t* streams, float* packed,
+                           uint32_t* streams_dev, void* stream);
 
 /* K3 pair emission in depth order, K4 stable tile sort, K5 tile ranges, K6 front-to-back compositing. */
 int gsr_forward_render(const GsrView*, const GsrGeom*, uint64_t n_pairs, GsrBinning*, GsrImages*, void* stream,
