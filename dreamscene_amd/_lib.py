@@ -239,6 +239,10 @@ SYMBOLS = [
     ("gsr_photo_forward", C.c_int, [C.POINTER(GsrPhotoViews), C.POINTER(GsrPhotoWeights), C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_size_t, C.c_void_p]),
     ("gsr_photo_backward", C.c_int, [C.POINTER(GsrPhotoViews), C.POINTER(GsrPhotoWeights), C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("gsr_model_init", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("gsr_opacity_reset", C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("gsr_densify_stats", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("gsr_backward", C.c_int, [C.POINTER(GsrView), C.POINTER(GsrGaussians), C.POINTER(GsrGeom), C.POINTER(GsrBinning),
                                C.POINTER(GsrImages), C.POINTER(GsrImageGrads), C.POINTER(GsrGrads), C.c_void_p,
                                C.c_void_p]),

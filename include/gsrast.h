@@ -712,6 +712,28 @@ int gsr_photo_forward(const GsrPhotoViews* views, const GsrPhotoWeights* weights
 int gsr_photo_backward(const GsrPhotoViews* views, const GsrPhotoWeights* weights, const float* saved, const float* dL_dloss,
                        void* stream);
 
+/* ---- model lifecycle: GaussianModel.create_from_pcd, reset_opacity and add_densification_stats(_div) (gs_renderer.py:582-608,
+ * :746-749 with :854-868, :1061-1080; dreamscene_amd/model.py; SEMANTICS.md section 15) -------------------------------------------
+ * Three element-wise kernels, one launch each on `stream`, no allocation, no host synchronisation, no memset (capturable).
+ * Every pointer is 4-byte aligned device memory; one rounding per operator, full-precision expf / logf / sqrtf and IEEE division.
+ * gsr_model_init     the six leaves of a new model of P rows with K = 1, 4, 9 or 16 SH coefficients per colour:
+ *                      xyz [P,3] = points;  f_dc [P,1,3] = (colors - 0.5f) / C0, C0 = fl32(0.28209479177387814);
+ *                      f_rest [P,K-1,3] = 0 (K == 1: not touched, NULL accepted);  scaling [P,3] = logf(sqrtf(fmaxf(dist2, 1e-7f)))
+ *                      in its three columns;  rotation [P,4] = (1,0,0,0);  opacity [P,1] = opacity_logit.
+ * gsr_opacity_reset  opacity_out[i] = logf(m / (1 - m)), m = min(s, cap) with a NaN s kept (torch.min), s = 1 / (1 + expf(-x));
+ *                    exp_avg and exp_avg_sq ([P], either may be NULL) are cleared. opacity_out is a tensor of its own: one that
+ *                    overlaps the input, or moments that overlap anything else of the call, are GSR_EINVAL.
+ * gsr_densify_stats  where filter[i] != 0 (uint8 / bool [n]): accum[i] += sqrtf(gx*gx + gy*gy) with (gx, gy) the first two
+ *                    entries of row start + i of grad [P_total,3], and denom[i] += 1 -- the expression the rasterizer backward
+ *                    uses for GsrGrads.stat_*, so both routes leave equal bits. 0 <= start, start + n <= P_total.
+ * Bad counts, NULL and misaligned pointers: GSR_EINVAL before any HIP call. P == 0 (n == 0) is valid and launches nothing. */
+int gsr_model_init(const float* points, const float* colors, const float* dist2, int32_t P, int32_t K, float opacity_logit,
+                   float* xyz, float* f_dc, float* f_rest, float* scaling, float* rotation, float* opacity, void* stream);
+int gsr_opacity_reset(const float* opacity, int32_t P, float cap, float* opacity_out, float* exp_avg, float* exp_avg_sq,
+                      void* stream);
+int gsr_densify_stats(const float* grad, int32_t P_total, const uint8_t* filter, int32_t start, int32_t n, float* accum,
+                      float* denom, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
