@@ -247,6 +247,20 @@ SYMBOLS = [
     ("gsr_kth_value", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     ("gsr_importance_filter", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    ("gsr_sample_env_indoor", C.c_int, [C.c_uint64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("gsr_sample_floor_indoor", C.c_int, [C.c_uint64, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
+    ("gsr_sample_shell", C.c_int, [C.c_uint64, C.c_float, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
+    ("gsr_sample_disc", C.c_int, [C.c_uint64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_void_p,
+                                  C.c_void_p, C.c_void_p]),
+    ("gsr_sample_ball", C.c_int, [C.c_uint64, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("gsr_sample_jitter", C.c_int, [C.c_uint64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]),
+    ("gsr_mesh_areas", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    ("gsr_sample_mesh", C.c_int, [C.c_uint64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("gsr_mesh_center", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     ("gsr_backward", C.c_int, [C.POINTER(GsrView), C.POINTER(GsrGaussians), C.POINTER(GsrGeom), C.POINTER(GsrBinning),
                                C.POINTER(GsrImages), C.POINTER(GsrImageGrads), C.POINTER(GsrGrads), C.c_void_p,
                                C.c_void_p]),

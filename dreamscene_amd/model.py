@@ -17,7 +17,8 @@ A DreamScene checkout binds it by making `gs_renderer.GaussianModel` a subclass 
 The remaining methods are torch one-liners, or torch restatements that exist so that code calling them keeps working
 (densify_and_clone, densify_and_split, densification_postfix, cat_tensors_to_optimizer, _prune_optimizer,
 replace_tensor_to_optimizer): they are not on any hot path here. Not provided: `extract_fields`, and the host-side samplers
-`init_pcd`, `init_env_pcd`, `init_floor_pcd`, which a checkout keeps (the constructor calls them when a subclass has them).
+`init_pcd`, `init_env_pcd`, `init_floor_pcd`, which a checkout keeps (the constructor calls them when a subclass has them;
+`pointcloud.SeededGaussianModel` is a subclass that draws them on the device from a seed).
 Decisions the reference leaves open: SEMANTICS.md section 15. No CPU fallback: the kernels refuse tensors that are not on a ROCm
 device with `GsrError`.
 """
@@ -267,7 +268,12 @@ class GaussianModel:
             raise ValueError(f"create_from_pcd: {P} points with {colors.shape[0]} colours")
         if K not in (1, 4, 9, 16):
             raise ValueError(f"create_from_pcd: sh_degree {self.max_sh_degree} is not 0..3")
-        points, colors = points.to(dev), colors.to(dev)
+        self._create_from_device(points.to(dev), colors.to(dev), require_grad, dist2, dev)
+
+    def _create_from_device(self, points: torch.Tensor, colors: torch.Tensor, require_grad, dist2: Optional[torch.Tensor], dev):
+        """The six leaves from contiguous fp32 [P,3] points and colours on the device `dev` (create_from_pcd's second half; what
+        pointcloud.SeededGaussianModel.create_from_cloud runs on a cloud that never was on the host)."""
+        P, K = points.shape[0], (self.max_sh_degree + 1) ** 2
         if dist2 is None:
             dist2 = knn.distCUDA2(points)
         else:

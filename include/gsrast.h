@@ -761,6 +761,50 @@ int gsr_importance_filter(const float* scaling, int32_t activated, const float* 
                           int32_t k_threshold, uint8_t* mask, float* v_list, int32_t* n_pruned, void* scratch,
                           size_t scratch_bytes, void* stream);
 
+/* ---- seeded point clouds: what GaussianModel.init_env_pcd, init_floor_pcd and init_pcd draw on the host (gs_renderer.py:218-408;
+ * dreamscene_amd/pointcloud.py; SEMANTICS.md section 17) ----------------------------------------------------------------------------
+ * points and colors are fp32 [rows,3] device memory, written from (seed, cloud id, index) alone: Philox-4x32-10 keyed by the seed,
+ * counter (index, block, cloud id, 3), uniforms of 24 bits in the open interval (0,1), uniform e of a row = slot e % 4 of block
+ * e / 4. The same seed gives the same bits on every device and for every launch geometry, and the first m rows of an n-row draw
+ * are the m-row draw (per sheet for the indoor env). fp32 arithmetic in the written order, IEEE division, full-precision sqrtf /
+ * cbrtf / sinf / cosf. One launch each on `stream`, nothing allocated, no host synchronisation (capturable).
+ * gsr_sample_env_indoor    5n rows in sheet order around box [6] (x0 y0 z0 x1 y1 z1), which is read from DEVICE memory
+ * gsr_sample_floor_indoor  n rows under box [6] (device memory) of colour (r, g, b)
+ * gsr_sample_shell         n rows of the shell radius * cbrt(0.95 .. 1.05), the upper half with zero_ground != 0
+ * gsr_sample_disc          n rows of the disc of `radius`, z in z0 - 0.1 .. z0
+ * gsr_sample_ball          n rows of the ball of `radius`, colours u / 255 * C0 + 0.5
+ * gsr_sample_jitter        n_seeds * copies rows: row (i, copy) = (x, -y, z + 0.15) of seed point i + the copy's offset (shared
+ *                          by every seed point, |offset| <= radius); colours seed_colors[i] + 1e-4 u, or the ball's with
+ *                          seed_colors == NULL
+ * gsr_mesh_areas           area [n_faces] (double): the fp32 area of each triangle of faces [n_faces,3] (int32) over vertices
+ *                          [n_vertices,3]; 0 for a face that names a vertex outside the table
+ * gsr_sample_mesh          n rows on the triangles chosen by cdf [n_faces] (double, non-decreasing, last entry 1: the first t with
+ *                          u < cdf[t]), axes swapped to (x, z, y); triangle [n] (int32, NULL accepted) receives each row's choice
+ * gsr_mesh_center          points[i] = (points[i] - fl32(mean)) / 80 with mean [3] doubles in device memory
+ * A row count outside 1 .. 2^31 - 1, a non-finite radius, NULL or misaligned pointers: GSR_EINVAL before any HIP call. */
+enum {
+  GSR_CLOUD_ENV = 0,
+  GSR_CLOUD_FLOOR = 1,
+  GSR_CLOUD_BALL = 2,
+  GSR_CLOUD_JITTER_OFFSETS = 3,
+  GSR_CLOUD_JITTER_COLORS = 4,
+  GSR_CLOUD_MESH = 5
+};
+int gsr_sample_env_indoor(uint64_t seed, const float* box, int32_t n, float* points, float* colors, void* stream);
+int gsr_sample_floor_indoor(uint64_t seed, const float* box, float r, float g, float b, int32_t n, float* points, float* colors,
+                            void* stream);
+int gsr_sample_shell(uint64_t seed, float radius, int32_t zero_ground, float r, float g, float b, int32_t n, float* points,
+                     float* colors, void* stream);
+int gsr_sample_disc(uint64_t seed, float radius, float z0, float r, float g, float b, int32_t n, float* points, float* colors,
+                    void* stream);
+int gsr_sample_ball(uint64_t seed, float radius, int32_t n, float* points, float* colors, void* stream);
+int gsr_sample_jitter(uint64_t seed, const float* seed_points, const float* seed_colors, int32_t n_seeds, int32_t copies,
+                      float radius, float* points, float* colors, void* stream);
+int gsr_mesh_areas(const float* vertices, int32_t n_vertices, const int32_t* faces, int32_t n_faces, double* area, void* stream);
+int gsr_sample_mesh(uint64_t seed, const float* vertices, int32_t n_vertices, const int32_t* faces, int32_t n_faces,
+                    const double* cdf, int32_t n, float* points, float* colors, int32_t* triangle, void* stream);
+int gsr_mesh_center(const double* mean, int32_t n, float* points, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
