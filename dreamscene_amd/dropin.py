@@ -97,7 +97,7 @@ class _Ring:
         best = None
         for s in free:
             cap = s.cv._cap
-            if cap is not None and getattr(cap, "ptr_sig", None) == ptr_sig:
+            if cap is not None and cap.ptr_sig == ptr_sig:
                 best = s
                 break
         if best is None:
@@ -107,8 +107,7 @@ class _Ring:
         if best is None and len(self.slots) < MAX_SLOTS:
             best = _Slot(rc)
             if self.slots:       # what the ring has learnt (pair counts, forward variant, warm-up) carries over
-                o = self.slots[0].cv
-                best.cv._peak_n, best.cv._fwd_mode, best.cv._warm = o._peak_n, o._fwd_mode, o._warm
+                best.cv.adopt(self.slots[0].cv)
             self.slots.append(best)
         if best is None and free:
             best = min(free, key=lambda s: s.stamp)

@@ -273,6 +273,15 @@ def uses_columns(P: int, H: int, W: int) -> bool:
 SEG_LEN_256_FROM = 8_000_000
 
 
+def capacity_grid(pairs: int) -> int:
+    """The pair capacity for `pairs` expected pairs (headroom included): 65536 more, rounded UP to a coarse grid (1/8 octave,
+    at least 65536) so that consecutive calls ask the caching allocator for identical block sizes (jittering sizes fragment
+    it and end in device-synchronising hipMalloc/hipFree calls: measured 3.5x slowdown after a few hundred views)."""
+    want = pairs + 65536
+    q = max(65536, 1 << max(0, want.bit_length() - 4))
+    return (want + q - 1) // q * q
+
+
 def pick_seg_len(cap, n_views: int = 1) -> int:
     env = os.environ.get("GSR_SEG_LEN")       # (tools / experiments: 64, 128 or 256 for every call)
     if env:
@@ -487,12 +496,8 @@ def _forward_steps(s: GaussianRasterizationSettings, means3D, opacities, shs, co
             keep_bufs = (buf, buf2)
             view_src = {k: (buf2, offs2[k]) if k in NSIZED else (buf, offs[k]) for k in offs}
         else:
-            # capacity = 1.5x the recent maximum, rounded UP to a coarse grid (1/8 octave) so that consecutive calls
-            # ask the caching allocator for identical block sizes (jittering sizes fragment it and end in
-            # device-synchronising hipMalloc/hipFree calls: measured 3.5x slowdown after a few hundred views)
-            want = int(hint * 1.5) + 65536
-            q = max(65536, 1 << max(0, want.bit_length() - 4))
-            cap = (want + q - 1) // q * q
+            # capacity = 1.5x the recent maximum, on the coarse grid
+            cap = capacity_grid(int(hint * 1.5))
             if capture:
                 cap = hint                       # the caller chose the capacity
             buf, ptrs, offs = alloc_state(cap)

@@ -28,7 +28,6 @@ from __future__ import annotations
 
 import ctypes as C
 import dataclasses
-import weakref
 from typing import List, Optional, Sequence
 
 import torch
@@ -38,7 +37,7 @@ from . import graph as G
 from . import rasterizer as R
 from . import scene as S
 from . import views as VW
-from .graph import WARM_CALLS, _Pending, capacity_for, poll_pair_counts, user_view
+from .graph import WARM_CALLS, user_view
 
 CAPTURABLE_K = (1, 4, 9, 16)
 
@@ -84,42 +83,21 @@ def _in_place_readable(models, dev) -> bool:
                for m in models for t in m)
 
 
-class _Captured:
-    """Static buffers + the graphs of one capture key and capacity."""
-    pass
+class _ModelsCapture(G.Captured):
+    """+ the scene module's own: noise buffers, stream-id words, gradients through the returned scales, backward graphs."""
+    __slots__ = ("sn", "hn", "words", "g_scales", "gC", "bwd", "bwd_m2d")
 
 
 class _CapturedModelsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, owner, settings_list, rc, scale_noise, sh_noise, specs, differentiable, means2D, *leaves):
         models = [tuple(leaves[6 * m:6 * m + 6]) for m in range(len(leaves) // 6)]
-        if (not differentiable) and owner._backward_pending():
-            outs, cap, eager_states = owner._eager_forward(settings_list, models, scale_noise, sh_noise, specs, rc)
-        else:
-            outs, cap, eager_states = owner._forward(settings_list, models, scale_noise, sh_noise, specs, rc)
-        ctx.owner, ctx.rc, ctx.cap_state, ctx.eager_states = owner, rc, cap, eager_states
-        ctx.generation = cap.generation if cap is not None else -1
-        ctx.pending = None
-        if differentiable and cap is not None:
-            ctx.pending = _Pending()
-            owner._pending = weakref.ref(ctx.pending)
-        ctx.set_materialize_grads(False)
-        flat = []
-        for (img, radii, da, sc) in outs:
-            ctx.mark_non_differentiable(radii)
-            flat += [img, radii, da, sc]
-        return tuple(flat)
+        return G.fn_forward(ctx, owner, rc, differentiable, settings_list, models, scale_noise, sh_noise, specs)
 
     @staticmethod
     def backward(ctx, *grads):
-        cap = ctx.cap_state
-        if cap is not None and cap.generation != ctx.generation:
-            # (graph.py, _CapturedFn.backward: the static state AND the outputs of a capture belong to its latest replay)
-            raise RuntimeError(
-                "CapturedModelsViews: backward of a forward whose captured state has been overwritten by a later forward "
-                f"(replay {ctx.generation}, now {cap.generation}); run backward before the next forward of the same "
-                "CapturedModelsViews, or use rasterize_models_views for calls whose graphs must stay alive")
-        o = ctx.owner._backward(cap, ctx.eager_states, grads, ctx.rc)
+        G.refuse_stale_backward(ctx)
+        o = ctx.owner._backward(ctx.cap_state, ctx.eager_states, grads, ctx.rc)
         if ctx.pending is not None:
             ctx.pending.done = True
         flat = []
@@ -128,26 +106,16 @@ class _CapturedModelsFn(torch.autograd.Function):
         return (None, None, None, None, None, None, None, o["dL_dmeans2D"], *flat)
 
 
-class CapturedModelsViews(torch.nn.Module):
+class CapturedModelsViews(G.CapturedModule):
     """`scene.rasterize_models_views` as a module whose steps replay from captured graphs. forward() takes the arguments of
     rasterize_models_views (the context is the module's) and applies its argument checks; image size and scale_modifier must
     stay the same from step to step, everything in `capture_key` re-captures when it changes."""
+    NAME, ALTERNATIVE = "CapturedModelsViews", "rasterize_models_views"
+    OUT_KEYS = ("color", "radii", "depth_alpha", "act_scales")
 
     def __init__(self, context=None, headroom: float = 1.5):
-        super().__init__()
-        self.context = context
-        self.headroom = float(headroom)
-        self._cap: Optional[_Captured] = None
+        super().__init__(context, headroom)
         self._key = None
-        self._warm = 0
-        self._peak_n = 0
-        self._fwd_mode = 0
-        self._pending = None        # weak reference to the _Pending of the latest differentiable captured forward
-        self.stats = dict(captures=0, replays=0, eager_steps=0, overflows=0)
-
-    def _backward_pending(self) -> bool:
-        p = self._pending() if self._pending is not None else None
-        return p is not None and not p.done
 
     # ------------------------------------------------------------------------------------------------ public
     def forward(self, settings_list: Sequence, models: Sequence, means2D: torch.Tensor,
@@ -183,10 +151,7 @@ class CapturedModelsViews(torch.nn.Module):
                        sh_noise=None if sh_noise is None else sh_noise[k],
                        noise=None if specs is None else specs[k]) for k in range(V)]
         res = VW.rasterize_views_forward_raw(settings_list, None, None, None, None, None, None, None, scenes=scenes, rc=rc)
-        self._peak_n = max([self._peak_n] + [int(o["N"]) for o, _ in res])
-        self._fwd_mode = int(res[-1][1].binning.fwd_mode)      # the compositing variant the eager path settled on
-        self.stats["eager_steps"] += 1
-        return [(o["color"], o["radii"], o["depth_alpha"], o["act_scales"]) for o, _ in res], None, [st for _, st in res]
+        return self._eager_result(res)
 
     def _forward(self, settings_list, models, scale_noise, sh_noise, specs, rc):
         eager = lambda: self._eager_forward(settings_list, models, scale_noise, sh_noise, specs, rc)
@@ -211,26 +176,13 @@ class CapturedModelsViews(torch.nn.Module):
                 self._warm += 1
                 return eager()
             self._cap = cap = self._capture(settings_list, models, scale_noise, sh_noise, specs, rc, P, K)
-        lib = L.load()
         stream = torch.cuda.current_stream(dev)
         with torch.cuda.device(dev):
-            self._write_step(lib, cap, settings_list, scale_noise, sh_noise, specs, rc, stream.cuda_stream)
-            cap.pinned_np[:] = -1
-            cap.generation += 1
-            cap.gF.replay()
-            cap.evF.record(stream)
-            poll_pair_counts(cap.pinned_np, V, cap.evF, rc.host_stats)
-        ns = [int(x) for x in cap.pinned_np[:V]]
-        self._peak_n = max([self._peak_n] + ns)
-        self.stats["replays"] += 1
-        if max(ns) > cap.cap or min(ns) < 0:
-            # a view outgrew the capacity (its lists were clamped): redo this step exactly, capture again next step
-            self.stats["overflows"] += 1
-            self._cap = None
-            return eager()
-        return cap.outs, cap, None
+            self._write_step(cap, settings_list, scale_noise, sh_noise, specs, rc, stream.cuda_stream)
+            ok = self._replay(cap, stream, rc)
+        return (cap.outs, cap, None) if ok else eager()
 
-    def _write_step(self, lib, cap, settings_list, scale_noise, sh_noise, specs, rc, stream) -> None:
+    def _write_step(self, cap, settings_list, scale_noise, sh_noise, specs, rc, stream) -> None:
         """This step's cameras and stream ids -> the device memory the captured views point into (one launch), its noise
         tensors -> the static buffers."""
         V = cap.V
@@ -239,96 +191,45 @@ class CapturedModelsViews(torch.nn.Module):
         if cap.words is not None:
             ids = (C.c_uint32 * V)(*[0 if (sp is None or isinstance(sp.stream, torch.Tensor)) else int(sp.stream)
                                      for sp in specs])
-        L.check(lib.gsr_pack_views_streams(V, structs, ids, cap.packed.data_ptr(),
-                                           None if cap.words is None else cap.words.data_ptr(), stream),
+        L.check(L.load().gsr_pack_views_streams(V, structs, ids, cap.packed.data_ptr(),
+                                                None if cap.words is None else cap.words.data_ptr(), stream),
                 "gsr_pack_views_streams")
         for bufs, src in ((cap.sn, scale_noise), (cap.hn, sh_noise)):
             if bufs is not None:
                 torch._foreach_copy_(bufs, [src[k] for k in range(V)])
 
-    def _capture(self, settings_list, models, scale_noise, sh_noise, specs, rc, P, K) -> _Captured:
-        lib = L.load()
+    def _capture(self, settings_list, models, scale_noise, sh_noise, specs, rc, P, K) -> _ModelsCapture:
         dev = models[0][0].device
         V = len(settings_list)
-        s0 = settings_list[0]
-        H, W = int(s0.image_height), int(s0.image_width)
-        cap = _Captured()
-        cap.P, cap.K, cap.V = P, K, V
-        cap.cap = capacity_for(self._peak_n, self.headroom)
-        f32 = torch.float32
-        with torch.cuda.device(dev):
-            cap.packed = torch.zeros((V, L.GSR_PACKED_VIEW_FLOATS), dtype=f32, device=dev)
-            cap.pinned = torch.zeros(VW.MAX_VIEWS, dtype=torch.int64).pin_memory()
-            cap.generation = 0
-            # every view its own noise buffers: separate allocations, so that each is 16-byte aligned whatever P is
-            new = lambda *shape: [torch.empty(shape, dtype=f32, device=dev) for _ in range(V)]
+        # every view its own noise buffers: separate allocations, so that each is 16-byte aligned whatever P is
+        new = lambda *shape: [torch.empty(shape, dtype=torch.float32, device=dev) for _ in range(V)]
+
+        def static_inputs(cap):
             cap.sn = new(P, 3) if scale_noise is not None else None
             cap.hn = new(P, K, 3) if sh_noise is not None else None
             # the stream ids of integer-stream specs: view k reads word k (consecutive words: one K1 / K8 pass serves the views)
             own = specs is not None and any(sp is not None and not isinstance(sp.stream, torch.Tensor) for sp in specs)
             cap.words = torch.zeros(V, dtype=torch.int32, device=dev) if own else None
-            views, scenes = [], []
-            for k, s in enumerate(settings_list):
-                row = cap.packed[k]
-                views.append(s._replace(bg=row[0:3], viewmatrix=row[4:20].view(4, 4), projmatrix=row[20:36].view(4, 4),
-                                        campos=row[36:39]))
+            scenes = []
+            for k in range(V):
                 sp = None if specs is None else specs[k]
                 if sp is not None and not isinstance(sp.stream, torch.Tensor):
                     sp = dataclasses.replace(sp, stream=cap.words[k:k + 1])
                 scenes.append(dict(models=models, scale_noise=None if cap.sn is None else cap.sn[k],
                                    sh_noise=None if cap.hn is None else cap.hn[k], noise=sp))
-            stride = R._align(int(lib.gsr_project_scratch_bytes(P)), 256)
-            cap.proj_scratch = torch.empty(stride * V + 4096, dtype=torch.uint8, device=dev)
-            sort_bytes = R._align(int(lib.gsr_sort_scratch_bytes(cap.cap, lib.gsr_num_tiles(H, W))), 256)
-            cap.sort_scratch = torch.empty(sort_bytes * V + 4096, dtype=torch.uint8, device=dev)
-            fwd_mode = int(rc.fwd_variant if rc.fwd_variant is not None else self._fwd_mode)
-            gens = [R._forward_steps(
-                views[k], None, None, None, None, None, None, None, False, False, "auto", scenes[k],
-                dict(scratch=cap.proj_scratch[k * stride:(k + 1) * stride], pinned=cap.pinned, index=k, event=None,
-                     sort=(lambda nbytes, k=k: cap.sort_scratch[k * sort_bytes:(k + 1) * sort_bytes]),
-                     capture=dict(cap=cap.cap, fwd_mode=fwd_mode), dynamic=cap.packed[k].data_ptr() + 40 * 4,
-                     seg_len=rc.seg_len or R.pick_seg_len(cap.cap, V)), rc) for k in range(V)]
-            heads = [next(g) for g in gens]
-            cap.views = (L.GsrView * V)(*[h[0] for h in heads])
-            cap.geoms = (L.GsrGeom * V)(*[h[1] for h in heads])
-            cap.gauss = (L.GsrGaussians * V)(*[h[2] for h in heads])
-            cap.bins = (L.GsrBinning * V)(*[h[3] for h in heads])
-            cap.imgs = (L.GsrImages * V)(*[h[4] for h in heads])
-            # a first, un-captured write fills the packed block and the words and proves the arguments before anything is recorded
-            self._write_step(lib, cap, settings_list, scale_noise, sh_noise, specs, rc,
-                             torch.cuda.current_stream(dev).cuda_stream)
-            torch.cuda.synchronize(dev)
-            cap.gF = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(cap.gF, capture_error_mode="thread_local"):
-                st = torch.cuda.current_stream(dev).cuda_stream
-                L.check(lib.gsr_forward_project_batch(V, cap.views, cap.gauss, cap.geoms, cap.pinned.data_ptr(), st, None),
-                        "gsr_forward_project_batch (capture)")
-                for k in range(V):
-                    heads[k][1].sorted_idx = cap.geoms[k].sorted_idx
-                L.check(lib.gsr_forward_render_batch(V, cap.views, cap.geoms, cap.cap, cap.bins, cap.imgs, st, None),
-                        "gsr_forward_render_batch (capture)")
-            res = []
-            for g in gens:
-                try:
-                    next(g)
-                    raise RuntimeError("forward generator did not finish")
-                except StopIteration as e:
-                    res.append(e.value)
-            cap.states = [st_ for _, st_ in res]
-            cap.outs = [(o["color"], o["radii"], o["depth_alpha"], o["act_scales"]) for o, _ in res]
-            # ---- backward: static upstream-gradient buffers (per view the gradient through the returned scales has its own
-            #      allocation: the library wants it 16-byte aligned); the results are allocated by the first backward
-            cap.g_color = torch.zeros((V, 3, H, W), dtype=f32, device=dev)
-            cap.g_da = torch.zeros((V, 2, H, W), dtype=f32, device=dev)
-            cap.g_scales = new(P, 3)
-            cap.bwd = None
-            cap.gC = {}              # which views have a gradient through their scales, or the caller's gradient addresses -> graph C
-            cap.evF = torch.cuda.Event()
-            cap.pinned_np = cap.pinned.numpy()       # the same page-locked words, readable without a torch call
-        self.stats["captures"] += 1
+            return [(None, None, None, None, None, scene) for scene in scenes]
+
+        # (the first, un-captured write fills the words too)
+        cap = G.capture_forward(
+            self, _ModelsCapture, settings_list, P, K, rc, dev, static_inputs,
+            lambda cap, stream: self._write_step(cap, settings_list, scale_noise, sh_noise, specs, rc, stream))
+        # per view the gradient through the returned scales has its own allocation: the library wants it 16-byte aligned
+        cap.g_scales = new(P, 3)
+        cap.bwd = None
+        cap.gC = {}              # which views have a gradient through their scales, or the caller's gradient addresses -> graph C
         return cap
 
-    def _backward_call(self, cap: _Captured, rc, has_gs, first: bool = False, direct=None):
+    def _backward_call(self, cap: _ModelsCapture, rc, has_gs, first: bool = False, direct=None):
         """The backward over the static buffers (or, direct = (gcs, gdas, gss), over the caller's gradient tensors): once
         eagerly into fresh tensors (`first`: they become the static results and nothing of the caller's is touched -- no buffer
         added to, no statistics), then under capture."""
@@ -342,7 +243,7 @@ class CapturedModelsViews(torch.nn.Module):
             cap.states, gcs, gdas, model_grads=bufs if bufs is not None else cap.bwd["model_grads"],
             accumulate=bufs is not None, stats=rc.densify_stats, stats_views=rc.stats_views, reuse=cap.bwd, **kw)
 
-    def _graph_c(self, cap: _Captured, rc, has_gs, direct=None):
+    def _graph_c(self, cap: _ModelsCapture, rc, has_gs, direct=None):
         """Graph C of one pattern of scale gradients over the static buffers, or -- direct -- over the caller's own gradient
         tensors (graph.py, _direct_graph: a loss produces its gradients at the same addresses step after step, and then
         nothing is copied); None when the direct graphs are used up."""
@@ -368,16 +269,12 @@ class CapturedModelsViews(torch.nn.Module):
                 self.stats["captures_bwd_direct"] = self.stats.get("captures_bwd_direct", 0) + 1
         return g
 
-    def _backward(self, cap: Optional[_Captured], eager_states, grads, rc):
+    def _backward(self, cap: Optional[_ModelsCapture], eager_states, grads, rc):
         V = len(grads) // 4
         gss = [grads[4 * k + 3] for k in range(V)]
         bufs = rc.model_grad_buffers
         if cap is None:            # a warm-up / overflow / uncapturable step: the eager backward on the eager states
-            st0 = eager_states[0]
-            H, W, dev = st0.view.image_height, st0.view.image_width, st0.dev
-            z = lambda c: torch.zeros((c, H, W), dtype=torch.float32, device=dev)
-            gcs = [grads[4 * k] if grads[4 * k] is not None else z(3) for k in range(V)]
-            gdas = [grads[4 * k + 2] if grads[4 * k + 2] is not None else z(2) for k in range(V)]
+            gcs, gdas = G.eager_upstream(eager_states, grads, 4)
             return R.rasterize_backward_views_scene_raw(eager_states, gcs, gdas, model_grads=bufs, accumulate=bufs is not None,
                                                         dL_dscales_outs=gss if any(g is not None for g in gss) else None,
                                                         stats=rc.densify_stats, stats_views=rc.stats_views, profile=rc.profile)
@@ -387,25 +284,10 @@ class CapturedModelsViews(torch.nn.Module):
             # pattern; a trainer's pattern does not change)
             has_gs = tuple(g is not None for g in gss)
             gcs, gdas = [grads[4 * k] for k in range(V)], [grads[4 * k + 2] for k in range(V)]
-            f32 = torch.float32
-            usable = all(g is not None and g.dtype == f32 and g.is_contiguous() and g.data_ptr() % 4 == 0 for g in gcs + gdas) \
-                and all(g is None or (g.dtype == f32 and g.is_contiguous() and g.data_ptr() % 16 == 0
-                                      and tuple(g.shape) == (cap.P, 3)) for g in gss)
+            usable = G.direct_usable(gcs, gdas, gss, cap.P)
             graph_c = self._graph_c(cap, rc, has_gs, direct=(gcs, gdas, gss)) if usable else None
             if graph_c is None:
                 graph_c = self._graph_c(cap, rc, has_gs)
-                dst, src = [], []
-                for k in range(V):
-                    for buf, g in ((cap.g_color[k], gcs[k]), (cap.g_da[k], gdas[k])):
-                        if g is None:
-                            buf.zero_()
-                        else:
-                            dst.append(buf)
-                            src.append(g)
-                    if gss[k] is not None:
-                        dst.append(cap.g_scales[k])
-                        src.append(gss[k])
-                if dst:
-                    torch._foreach_copy_(dst, src)
+                G.stage_upstream(cap, gcs, gdas, cap.g_scales, gss)
             graph_c.replay()
         return dict(dL_dmeans2D=cap.bwd_m2d, model_grads=cap.bwd["model_grads"])
