@@ -33,6 +33,7 @@ SOURCES = {
     "model.hip": ["-ffp-contract=off"],
     "select.hip": ["-ffp-contract=off"],
     "sample.hip": ["-ffp-contract=off"],
+    "fields.hip": ["-ffp-contract=off"],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-fp-atomics", "-fno-gpu-rdc",
           "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-Wall", "-Wno-unused-function"]

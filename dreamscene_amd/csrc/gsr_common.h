@@ -128,6 +128,19 @@ __device__ __forceinline__ int32_t gsr_f2i_sat_fast(float x) {
   return i;
 }
 
+// ---- the order-preserving 32-bit key of a float (sign bit of non-negatives flipped, all bits of negatives flipped, every NaN the
+// largest key): unsigned integer comparisons and atomics on keys order the floats (select.hip's radix select, fields.hip's bounds)
+__device__ __forceinline__ uint32_t gsr_float_key(float f) {
+  const uint32_t u = __float_as_uint(f);
+  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0xFFFFFFFFu;           // every NaN, either sign: after +inf
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ __forceinline__ float gsr_key_float(uint32_t key) {
+  if (key == 0xFFFFFFFFu) return __uint_as_float(0x7FC00000u);
+  return __uint_as_float((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key);
+}
+
 // ---- wave64 cross-lane reductions on DPP (no LDS traffic) ---------------------------------------------------
 template <int CTRL, int ROW_MASK = 0xF, int BANK_MASK = 0xF, bool BOUND = true>
 __device__ __forceinline__ float gsr_dpp(float v) {

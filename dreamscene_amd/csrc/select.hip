@@ -33,17 +33,6 @@ static_assert((kValuesAt * 4) % 16 == 0, "the values start on a 16-byte boundary
 
 enum { kPlain = 0, kVolume = 1, kScore = 2 };    // what a pass's element is
 
-__device__ __forceinline__ uint32_t key_of(float f) {
-  const uint32_t u = __float_as_uint(f);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return 0xFFFFFFFFu;           // every NaN, either sign: after +inf
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ float value_of(uint32_t key) {
-  if (key == 0xFFFFFFFFu) return __uint_as_float(0x7FC00000u);
-  return __uint_as_float((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key);
-}
-
 struct Chosen {
   uint32_t prefix;                               // the key's leading 8 * npass bits, in place
   uint32_t k;                                    // the rank among the elements that share them
@@ -109,7 +98,7 @@ __global__ void __launch_bounds__(kT) k_select_pass(const PassArgs a) {
   for (int j = 0; j < kWaves; ++j) s_hist[j][tid] = 0u;
   float kth = 0.f;
   if (MODE == kScore) {
-    kth = value_of(derive(a.hist_prev, kPasses, a.k_prev, s_wave, s_sel).prefix);
+    kth = gsr_key_float(derive(a.hist_prev, kPasses, a.k_prev, s_wave, s_sel).prefix);
     if (blockIdx.x == 0 && tid == 0) a.state[0] = kth;
   }
   uint32_t prefix = 0u, care = 0u;
@@ -140,7 +129,7 @@ __global__ void __launch_bounds__(kT) k_select_pass(const PassArgs a) {
       } else {
         f = a.x[i];
       }
-      const uint32_t key = key_of(f);
+      const uint32_t key = gsr_float_key(f);
       if (((key ^ prefix) & care) == 0u) atomicAdd(&s_hist[w][(key >> shift) & 255u], 1u);
     }
   }
@@ -159,7 +148,7 @@ __global__ void __launch_bounds__(kT) k_select_clear(uint32_t* __restrict__ word
 __global__ void __launch_bounds__(kT) k_select_finish(const uint32_t* __restrict__ hist, const uint32_t k, float* __restrict__ out) {
   __shared__ uint32_t s_wave[kWaves];
   __shared__ uint32_t s_sel[2];
-  const float v = value_of(derive(hist, kPasses, k, s_wave, s_sel).prefix);
+  const float v = gsr_key_float(derive(hist, kPasses, k, s_wave, s_sel).prefix);
   if (threadIdx.x == 0) *out = v;
 }
 
@@ -169,7 +158,7 @@ __global__ void __launch_bounds__(kT) k_filter_mask(const float* __restrict__ v,
   __shared__ uint32_t s_wave[kWaves];
   __shared__ uint32_t s_sel[2];
   const int tid = threadIdx.x, lane = tid & (GSR_WAVE - 1), w = tid / GSR_WAVE;
-  const float thr = value_of(derive(hist, kPasses, k, s_wave, s_sel).prefix);
+  const float thr = gsr_key_float(derive(hist, kPasses, k, s_wave, s_sel).prefix);
   if (blockIdx.x == 0 && tid == 0) state[1] = thr;
   uint32_t mine = 0u;
   for (uint64_t base = (uint64_t)blockIdx.x * kBlockItems; base < n; base += (uint64_t)gridDim.x * kBlockItems) {

@@ -10,15 +10,16 @@ A DreamScene checkout binds it by making `gs_renderer.GaussianModel` a subclass 
   densify_and_prune / prune /
   prune_points / prune_gaussians      densify.* and densify.importance_prune_mask
   save_ply / load_ply                 ply
+  extract_fields                      fields.extract_fields: five launches and one host read (csrc/fields.hip)
   max_radii2D / xyz_gradient_accum /
   denom                               views of the `densify.DensifyStats` at `self.stats`, which `stats.collect(...)` can also fill
                                       from inside the rasterizer backward
 
 The remaining methods are torch one-liners, or torch restatements that exist so that code calling them keeps working
 (densify_and_clone, densify_and_split, densification_postfix, cat_tensors_to_optimizer, _prune_optimizer,
-replace_tensor_to_optimizer): they are not on any hot path here. Not provided: `extract_fields`, and the host-side samplers
-`init_pcd`, `init_env_pcd`, `init_floor_pcd`, which a checkout keeps (the constructor calls them when a subclass has them;
-`pointcloud.SeededGaussianModel` is a subclass that draws them on the device from a seed).
+replace_tensor_to_optimizer): they are not on any hot path here. Not provided: the host-side samplers `init_pcd`, `init_env_pcd`,
+`init_floor_pcd`, which a checkout keeps (the constructor calls them when a subclass has them; `pointcloud.SeededGaussianModel` is
+a subclass that draws them on the device from a seed).
 Decisions the reference leaves open: SEMANTICS.md section 15. No CPU fallback: the kernels refuse tensors that are not on a ROCm
 device with `GsrError`.
 """
@@ -234,6 +235,15 @@ class GaussianModel:
 
     def get_covariance(self, scaling_modifier=1):
         return self.covariance_activation(self.get_scaling, scaling_modifier, self._rotation)
+
+    @torch.no_grad()
+    def extract_fields(self, resolution=128, num_blocks=16, relax_ratio=1.5):
+        """The opacity-weighted density on a resolution^3 grid, fp32 on the device; sets `center` (fp32 [3], device) and `scale`
+        (float), the normalisation of the kept rows, as the reference does."""
+        from . import fields
+        result = fields.extract_fields(self._xyz, self._opacity, self._scaling, self._rotation, resolution, num_blocks, relax_ratio)
+        self.center, self.scale = result.center, result.scale
+        return result.occ
 
     def oneupSHdegree(self):
         if self.active_sh_degree < self.max_sh_degree:

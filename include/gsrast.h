@@ -805,6 +805,34 @@ int gsr_sample_mesh(uint64_t seed, const float* vertices, int32_t n_vertices, co
                     const double* cdf, int32_t n, float* points, float* colors, int32_t* triangle, void* stream);
 int gsr_mesh_center(const double* mean, int32_t n, float* points, void* stream);
 
+/* ---- occupancy field: GaussianModel.extract_fields (gs_renderer.py:490-573 with gaussian_3d_coeff, :95-121; dreamscene_amd/
+ * fields.py; SEMANTICS.md section 18) -----------------------------------------------------------------------------------------------
+ * The opacity-weighted density of P Gaussians on a resolution^3 grid, fp32, from the raw leaves xyz [P,3], opacity_raw [P] (logits),
+ * scaling_raw [P,3] (log-scales) and rotation_raw [P,4] (any length, real part first). A row takes part iff sigmoid(opacity_raw) >
+ * 0.005. The axis is cut into n_chunks = ceil(resolution / split_size) chunks of split_size coordinates (the last may be shorter);
+ * a row belongs to chunk triple (cx, cy, cz) iff gate_lo[c] < its normalised centre < gate_hi[c], strictly, on every axis, and
+ * occ[x][y][z] = the sum over the members of the voxel's triple, in index order, of opacity * expf(power) (0 where power > 0).
+ * scratch: gsr_fields_scratch_bytes(P) bytes (0: P is not accepted), 16-byte aligned, the caller's; its contents on entry do not
+ * matter; too small: GSR_ESCRATCH. Nothing is allocated, no memset, no atomics on floats: the same bits on every run.
+ * gsr_fields_bounds    three launches. Writes the first 8 words of the scratch: the per-axis minimum [3] and maximum [3] of xyz over
+ *                      the rows that take part (fp32, exact; NaN where none does or an entry is NaN), their number (int32), 0.
+ *                      Reading them is the caller's one host read; center and scale follow from them on the host.
+ * gsr_extract_fields   two launches, nothing read by the host. center [3] is HOST memory; a row's normalised centre is (xyz -
+ *                      center) * scale and its standard deviations expf(scaling_raw) * scale. coords [resolution], gate_lo
+ *                      [n_chunks] and gate_hi [n_chunks] are device tables the kernels never recompute (the reference forms them on
+ *                      the host: torch.linspace(-1, 1, resolution), and a chunk's first / last coordinate -/+ the relaxed block
+ *                      size), both gates ascending. Every element of occ [resolution]^3 is written exactly once; occ needs no
+ *                      clearing. It does not read the head gsr_fields_bounds wrote.
+ * P <= 0, resolution outside 1 .. 1024, split_size outside 1 .. resolution, n_chunks != ceil(resolution / split_size) or > 255, a
+ * non-finite center or scale, NULL or misaligned (4 bytes; scratch 16) pointers, buffers that overlap occ or the scratch: GSR_EINVAL
+ * before any HIP call. */
+size_t gsr_fields_scratch_bytes(int32_t P);
+int gsr_fields_bounds(const float* xyz, const float* opacity_raw, int32_t P, void* scratch, size_t scratch_bytes, void* stream);
+int gsr_extract_fields(const float* xyz, const float* opacity_raw, const float* scaling_raw, const float* rotation_raw, int32_t P,
+                       const float* center, float scale, const float* coords, const float* gate_lo, const float* gate_hi,
+                       int32_t resolution, int32_t split_size, int32_t n_chunks, float* occ, void* scratch, size_t scratch_bytes,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
