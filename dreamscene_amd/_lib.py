@@ -1,281 +1,157 @@
-"""ctypes binding of libgsrast.so (the C ABI in include/gsrast.h). Fails loudly when the HIP library is
-missing or does not export the declared symbols: there is NO CPU / PyTorch fallback in the product path."""
+"""ctypes binding of libgsrast.so, derived from the C ABI in include/gsrast.h: the structures, the constants and the
+signatures below are read from the header at import, nothing of it is restated here. Fails loudly when the HIP library
+is missing or does not export the declared symbols: there is NO CPU / PyTorch fallback in the product path."""
 from __future__ import annotations
 
 import ctypes as C
 import os
+import re
+from types import SimpleNamespace
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # GSR_LIB: an experimental build of the same library (dreamscene_amd/build.py, A/B measurements); default: the product
 LIB_PATH = os.environ.get("GSR_LIB") or os.path.join(_HERE, "libgsrast.so")
-
-STAGES = ["preprocess", "scan", "duplicate", "sort", "ranges", "render_fwd", "render_bwd", "preprocess_bwd"]
-
-_f = C.c_void_p  # device pointers travel as integers
-
-
-class GsrView(C.Structure):
-    _fields_ = [("P", C.c_int32), ("sh_stride", C.c_int32), ("sh_degree", C.c_int32),
-                ("image_height", C.c_int32), ("image_width", C.c_int32),
-                ("tanfovx", C.c_float), ("tanfovy", C.c_float), ("scale_modifier", C.c_float),
-                ("prefiltered", C.c_int32), ("score_mode", C.c_int32),
-                ("bg", _f), ("viewmatrix", _f), ("projmatrix", _f), ("campos", _f), ("dynamic", _f)]
-
-
-GSR_MAX_MODELS = 16
-GSR_NOISE_SCALES, GSR_NOISE_SHS = 1, 2     # GsrScene.noise_flags
-GSR_PACKED_VIEW_FLOATS = 44
-GSR_PARTIAL_WORDS = 32     # 32-bit words per Gaussian of GsrGrads.partials (16 doubles, 12 used)
-
-
-class GsrModel(C.Structure):
-    _fields_ = [("count", C.c_int32), ("reserved_", C.c_int32), ("xyz", _f), ("scaling", _f), ("rotation", _f),
-                ("opacity", _f), ("features_dc", _f), ("features_rest", _f)]
-
-
-class GsrScene(C.Structure):
-    _fields_ = [("n_models", C.c_int32), ("reserved_", C.c_int32), ("models", GsrModel * GSR_MAX_MODELS),
-                ("scale_noise", _f), ("sh_noise", _f), ("scales_out", _f), ("rotations_out", _f),
-                ("opacities_out", _f), ("noise_seed", C.c_uint64), ("noise_stream_dev", _f),
-                ("noise_stream", C.c_uint32), ("noise_flags", C.c_uint32)]
-
-
-class GsrModelGrads(C.Structure):
-    _fields_ = [("xyz", _f), ("scaling", _f), ("rotation", _f), ("opacity", _f), ("features_dc", _f),
-                ("features_rest", _f)]
-
-
-class GsrSceneGrads(C.Structure):
-    _fields_ = [("models", GsrModelGrads * GSR_MAX_MODELS), ("dL_dscales_out", _f)]
-
-
-class GsrGaussians(C.Structure):
-    _fields_ = [("means3D", _f), ("opacities", _f), ("shs", _f), ("colors_precomp", _f), ("scales", _f),
-                ("rotations", _f), ("cov3D_precomp", _f), ("scene", C.POINTER(GsrScene))]
-
-
-class GsrGeom(C.Structure):
-    _fields_ = [("splat", _f), ("radii", _f), ("tiles_touched", _f), ("block_offsets", _f), ("scratch", _f),
-                ("scratch_bytes", C.c_size_t), ("sorted_idx", _f)]
-
-
-class GsrBinning(C.Structure):
-    _fields_ = [("point_list", _f), ("ranges", _f), ("tile_work", _f), ("bwd_items_cap", C.c_uint32),
-                ("seg_len", C.c_uint32), ("keys_sorted", _f), ("scratch", _f), ("scratch_bytes", C.c_size_t),
-                ("count_on_device", C.c_int32), ("fwd_mode", C.c_int32), ("stats_host", _f)]
-
-
-class GsrImages(C.Structure):
-    _fields_ = [("color", _f), ("depth_alpha", _f), ("final_T", _f), ("n_contrib", _f), ("tile_depth", _f),
-                ("ckpt", _f), ("important_score", _f)]
-
-
-class GsrImageGrads(C.Structure):
-    _fields_ = [("dL_dcolor", _f), ("dL_ddepth_alpha", _f)]
-
-
-class GsrGrads(C.Structure):
-    _fields_ = [("dL_dmeans3D", _f), ("dL_dmeans2D", _f), ("dL_dopacities", _f), ("dL_dshs", _f), ("dL_dcolors", _f),
-                ("dL_dscales", _f), ("dL_drotations", _f), ("dL_dcov3D", _f), ("dL_dview", _f), ("dL_dproj", _f),
-                ("dL_dcampos", _f), ("partials", _f), ("accumulate", C.c_int32), ("reserved_", C.c_int32),
-                ("stat_max_radii2D", _f), ("stat_xyz_gradient_accum", _f), ("stat_denom", _f),
-                ("scene", C.POINTER(GsrSceneGrads)), ("reached_mask", C.c_void_p),
-                ("reach", C.c_void_p), ("scratch_clean", C.c_int32), ("zero_outside", C.c_int32)]
-
-
-class GsrAdamGroup(C.Structure):
-    _fields_ = [("param", _f), ("grad", _f), ("exp_avg", _f), ("exp_avg_sq", _f), ("numel", C.c_int64),
-                ("lr", C.c_float), ("reserved_", C.c_float)]
-
-
-GSR_MAX_ADAM_GROUPS = 32
-GSR_ROWSET_MAX_REGIONS = 8
-
-
-class GsrRowRegion(C.Structure):
-    _fields_ = [("ptr", _f), ("width", C.c_int32), ("stride", C.c_int32)]
-
-
-class GsrRowSet(C.Structure):
-    _fields_ = [("rows", C.c_int32), ("n_regions", C.c_int32), ("regions", GsrRowRegion * GSR_ROWSET_MAX_REGIONS)]
-
-
-GSR_MAX_DISP_VIEWS = 16
-GSR_DISP_STATS_FLOATS = 4
-
-
-class GsrDispViews(C.Structure):
-    _fields_ = [("n_views", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("reserved_", C.c_int32),
-                ("depth_alpha", _f * GSR_MAX_DISP_VIEWS), ("dL_ddepth_alpha", _f * GSR_MAX_DISP_VIEWS),
-                ("focal", C.c_float * GSR_MAX_DISP_VIEWS)]
-
-
-GSR_DENSIFY_TENSORS = 6
-GSR_DENSIFY_MAX_SPLIT = 8
-GSR_DENSIFY_SIZE_WORDS = 16
-GSR_DENSIFY_NAMES = ("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation")     # GSR_DENSIFY_XYZ ... in table order
-
-
-class GsrDensifyPlan(C.Structure):
-    _fields_ = [("P", C.c_int32), ("N", C.c_int32), ("densify", C.c_int32), ("use_screen_size", C.c_int32),
-                ("scaling", _f), ("opacity", _f), ("xyz_gradient_accum", _f), ("denom", _f), ("max_radii2D", _f),
-                ("max_grad", C.c_float), ("dense_threshold", C.c_float), ("min_opacity", C.c_float),
-                ("world_size_threshold", C.c_float), ("max_screen_size", C.c_float), ("child_divisor", C.c_float)]
-
-
-class GsrDensifyTensor(C.Structure):
-    _fields_ = [("src", _f), ("dst", _f), ("m1_src", _f), ("m1_dst", _f), ("m2_src", _f), ("m2_dst", _f),
-                ("width", C.c_int32), ("reserved_", C.c_int32)]
-
-
-class GsrDensifyTable(C.Structure):
-    _fields_ = [("t", GsrDensifyTensor * GSR_DENSIFY_TENSORS), ("stat_src", _f * 3), ("stat_dst", _f * 3), ("noise", _f),
-                ("seed", C.c_uint64), ("P", C.c_int32), ("N", C.c_int32), ("n_survivors", C.c_int32), ("n_clones", C.c_int32),
-                ("n_children", C.c_int32), ("P_out", C.c_int32), ("zero_stats", C.c_int32), ("child_divisor", C.c_float)]
-
-
-class GsrPlacement(C.Structure):
-    _fields_ = [("P", C.c_int32), ("K", C.c_int32), ("xyz", _f), ("scaling", _f), ("rotation", _f), ("opacity", _f),
-                ("features_dc", _f), ("features_rest", _f), ("xyz_out", _f), ("scaling_out", _f), ("rotation_out", _f),
-                ("features_rest_out", _f), ("rs", C.c_float * 9), ("t", C.c_float * 3), ("log_scale", C.c_float * 3),
-                ("q", C.c_float * 4), ("m1", C.c_float * 9), ("m2", C.c_float * 25), ("m3", C.c_float * 49),
-                ("ground", C.c_int32), ("bounds", _f), ("t_effective", _f)]
-
-
-GSR_MAX_FRAME_VIEWS = 16
-
-
-class GsrFrameViews(C.Structure):
-    _fields_ = [("n_views", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("reserved_", C.c_int32),
-                ("image", _f * GSR_MAX_FRAME_VIEWS), ("depth_alpha", _f * GSR_MAX_FRAME_VIEWS)]
-
-
-GSR_MAX_PHOTO_VIEWS = 16
-GSR_MAX_PHOTO_CHANNELS = 4
-GSR_PHOTO_WINDOW = 11
-
-
-class GsrPhotoViews(C.Structure):
-    _fields_ = [("n_views", C.c_int32), ("channels", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
-                ("target_is_half", C.c_int32), ("round_image_to_half", C.c_int32),
-                ("image", _f * GSR_MAX_PHOTO_VIEWS), ("target", _f * GSR_MAX_PHOTO_VIEWS),
-                ("dL_dimage", _f * GSR_MAX_PHOTO_VIEWS)]
-
-
-class GsrPhotoWeights(C.Structure):
-    _fields_ = [("l2", C.c_float), ("l1", C.c_float), ("dssim", C.c_float)]
-
-
-# every symbol include/gsrast.h declares: (name, restype, argtypes)
-SYMBOLS = [
-    ("gsr_adam_step", C.c_int, [C.POINTER(GsrAdamGroup), C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,
-                                C.c_int32, C.c_void_p]),
-    ("gsr_version", C.c_int, []),
-    ("gsr_strerror", C.c_char_p, [C.c_int]),
-    ("gsr_last_hip_error", C.c_int, []),
-    ("gsr_project_scratch_bytes", C.c_size_t, [C.c_int32]),
-    ("gsr_sort_scratch_bytes", C.c_size_t, [C.c_uint64, C.c_uint32]),
-    ("gsr_num_tiles", C.c_uint32, [C.c_int32, C.c_int32]),
-    ("gsr_num_blocks", C.c_uint32, [C.c_int32]),
-    ("gsr_profile_create", C.c_void_p, []),
-    ("gsr_profile_destroy", None, [C.c_void_p]),
-    ("gsr_profile_set_stage_mask", None, [C.c_void_p, C.c_uint32]),
-    ("gsr_profile_set_sampling", None, [C.c_void_p, C.c_uint32]),
-    ("gsr_profile_collect", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
-    ("gsr_forward_project", C.c_int, [C.POINTER(GsrView), C.POINTER(GsrGaussians), C.POINTER(GsrGeom),
-                                      C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p]),
-    ("gsr_forward_project_async", C.c_int, [C.POINTER(GsrView), C.POINTER(GsrGaussians), C.POINTER(GsrGeom),
-                                            C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("gsr_forward_project_batch", C.c_int, [C.c_int32, C.POINTER(GsrView), C.POINTER(GsrGaussians), C.POINTER(GsrGeom),
-                                            C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("gsr_pack_views", C.c_int, [C.c_int32, C.POINTER(GsrView), C.c_void_p, C.c_void_p]),
-    ("gsr_pack_views_streams", C.c_int, [C.c_int32, C.POINTER(GsrView), C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p,
-                                         C.c_void_p]),
-    ("gsr_forward_render", C.c_int, [C.POINTER(GsrView), C.POINTER(GsrGeom), C.c_uint64, C.POINTER(GsrBinning),
-                                     C.POINTER(GsrImages), C.c_void_p, C.c_void_p]),
-    ("gsr_backward_views", C.c_int, [C.c_int32, C.POINTER(GsrView), C.POINTER(GsrGaussians), C.POINTER(GsrGeom),
-                                     C.POINTER(GsrBinning), C.POINTER(GsrImages), C.POINTER(GsrImageGrads),
-                                     C.POINTER(GsrGrads), C.c_void_p, C.c_void_p]),
-    ("gsr_forward_render_batch", C.c_int, [C.c_int32, C.POINTER(GsrView), C.POINTER(GsrGeom), C.c_uint64,
-                                           C.POINTER(GsrBinning), C.POINTER(GsrImages), C.c_void_p, C.c_void_p]),
-    ("gsr_rows_scratch_bytes", C.c_size_t, [C.c_int32]),
-    ("gsr_rows_pack", C.c_int, [C.POINTER(GsrRowSet), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
-                                C.c_size_t, C.c_void_p]),
-    ("gsr_rows_unpack", C.c_int, [C.POINTER(GsrRowSet), C.c_void_p, C.c_void_p, C.c_uint32, C.c_int64, C.c_int32, C.c_void_p,
-                                  C.c_void_p]),
-    ("gsr_sum_slices", C.c_int, [C.c_void_p, C.c_int32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
-    ("gsr_rowmsg_bytes", C.c_size_t, [C.c_int32, C.c_int32, C.c_uint32]),
-    ("gsr_rowmsg_pack", C.c_int, [C.POINTER(GsrRowSet), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
-    ("gsr_rowmsg_apply", C.c_int, [C.POINTER(GsrRowSet), C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p,
-                                   C.c_void_p]),
-    ("gsr_rowmsg_pack_slices", C.c_int, [C.POINTER(GsrRowSet), C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_uint32,
-                                         C.c_void_p]),
-    ("gsr_rowmsg_reduce", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.c_int32, C.c_uint32, C.c_void_p,
-                                    C.c_uint32, C.c_void_p]),
-    ("gsr_rowmsg_apply_slices", C.c_int, [C.POINTER(GsrRowSet), C.c_void_p, C.c_uint64, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p,
-                                          C.c_void_p, C.c_void_p]),
-    ("gsr_knn_scratch_bytes", C.c_size_t, [C.c_int32]),
-    ("gsr_knn_mean_dist2", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    ("gsr_disp_scratch_bytes", C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
-    ("gsr_disp_forward", C.c_int, [C.POINTER(GsrDispViews), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                   C.c_void_p]),
-    ("gsr_disp_backward", C.c_int, [C.POINTER(GsrDispViews), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
-                                    C.c_void_p]),
-    ("gsr_tv_scratch_bytes", C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
-    ("gsr_tv_forward", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t,
-                                 C.c_void_p]),
-    ("gsr_tv_backward", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("gsr_densify_scratch_bytes", C.c_size_t, [C.c_int32, C.c_int32]),
-    ("gsr_densify_plan", C.c_int, [C.POINTER(GsrDensifyPlan), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("gsr_densify_plan_mask", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("gsr_densify_apply", C.c_int, [C.POINTER(GsrDensifyTable), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
-    ("gsr_noise_fill", C.c_int, [C.c_uint64, C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("gsr_place_scratch_bytes", C.c_size_t, [C.c_int32]),
-    ("gsr_place", C.c_int, [C.POINTER(GsrPlacement), C.c_void_p, C.c_size_t, C.c_void_p]),
-    ("gsr_frames_scratch_bytes", C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
-    ("gsr_frames_quantize", C.c_int, [C.POINTER(GsrFrameViews), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    ("gsr_photo_window", None, [C.POINTER(C.c_float)]),
-    ("gsr_photo_scratch_bytes", C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
-    ("gsr_photo_forward", C.c_int, [C.POINTER(GsrPhotoViews), C.POINTER(GsrPhotoWeights), C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_void_p, C.c_size_t, C.c_void_p]),
-    ("gsr_photo_backward", C.c_int, [C.POINTER(GsrPhotoViews), C.POINTER(GsrPhotoWeights), C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("gsr_model_init", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
-                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("gsr_opacity_reset", C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("gsr_densify_stats", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("gsr_select_scratch_bytes", C.c_size_t, [C.c_int32]),
-    ("gsr_kth_value", C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    ("gsr_importance_filter", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_void_p,
-                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    ("gsr_sample_env_indoor", C.c_int, [C.c_uint64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("gsr_sample_floor_indoor", C.c_int, [C.c_uint64, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_void_p,
-                                          C.c_void_p, C.c_void_p]),
-    ("gsr_sample_shell", C.c_int, [C.c_uint64, C.c_float, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_void_p,
-                                   C.c_void_p, C.c_void_p]),
-    ("gsr_sample_disc", C.c_int, [C.c_uint64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_void_p,
-                                  C.c_void_p, C.c_void_p]),
-    ("gsr_sample_ball", C.c_int, [C.c_uint64, C.c_float, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("gsr_sample_jitter", C.c_int, [C.c_uint64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p,
-                                    C.c_void_p]),
-    ("gsr_mesh_areas", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
-    ("gsr_sample_mesh", C.c_int, [C.c_uint64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
-                                  C.c_void_p, C.c_void_p, C.c_void_p]),
-    ("gsr_mesh_center", C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
-    ("gsr_fields_scratch_bytes", C.c_size_t, [C.c_int32]),
-    ("gsr_fields_bounds", C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
-    ("gsr_extract_fields", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_float), C.c_float,
-                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                     C.c_size_t, C.c_void_p]),
-    ("gsr_backward", C.c_int, [C.POINTER(GsrView), C.POINTER(GsrGaussians), C.POINTER(GsrGeom), C.POINTER(GsrBinning),
-                               C.POINTER(GsrImages), C.POINTER(GsrImageGrads), C.POINTER(GsrGrads), C.c_void_p,
-                               C.c_void_p]),
-]
-
-_lib = None
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "gsrast.h")
 
 
 class GsrError(RuntimeError):
     pass
+
+
+# ---- the header's grammar, and nothing else: whatever parse_header() does not recognise is an error ------------------------------
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint64_t": C.c_uint64,
+            "uint8_t": C.c_uint8, "size_t": C.c_size_t, "float": C.c_float, "double": C.c_double}
+_ITEM = re.compile(r"""
+    ^[ \t]*\#define[ \t]+(?P<define>GSR_\w+)[ \t]+(?P<value>\S+)[ \t]*$
+  | \benum\s*\{(?P<enum>[^{};]*)\}\s*;
+  | \btypedef\s+struct\s+(?P<opaque>\w+)\s+(?P=opaque)\s*;
+  | \btypedef\s+struct\s+(?P<struct>\w+)\s*\{(?P<fields>[^{}]*)\}\s*(?P=struct)\s*;
+  | \b(?P<ret>(?:const\s+)?\w+\s*\*?)\s*\b(?P<fn>gsr_\w+)\s*\((?P<params>[^(){};]*)\)\s*;
+""", re.M | re.X)
+_DECL = re.compile(r"(?:const\s+)?(\w+)\b(.*)", re.S)                        # base type, declarators
+_DECLARATOR = re.compile(r"\s*(\*?)\s*(\w+)?\s*(?:\[\s*(\w+)\s*\])?\s*")     # [*] [name] [[size]]
+_PREAMBLE = re.compile(r'#ifndef (\w+) #define \1 (?:#include <[\w./]+> )*#ifdef __cplusplus extern "C" \{ #endif '
+                       r'#ifdef __cplusplus \} #endif #endif')
+
+
+def parse_header(text: str, host_pointers: dict | None = None) -> SimpleNamespace:
+    """The ABI a header in gsrast.h's grammar declares, as ctypes: .constants {name: int} (#defines and enumerators), .enums
+    [{name: int}] (one per enum), .structs {name: Structure subclass}, .symbols [(name, restype, argtypes)]. A pointer to a Gsr
+    struct becomes POINTER(struct), any other pointer c_void_p (device pointers travel as integers) -- except the parameters
+    host_pointers {(function, parameter): ctypes type} names. A pure function of its arguments."""
+    abi = SimpleNamespace(constants={}, enums=[], structs={}, symbols=[], opaque=set())
+    pending = dict(host_pointers or {})
+
+    def const(name, value):
+        if name in abi.constants:
+            raise GsrError(f"gsrast.h: {name} is defined twice")
+        abi.constants[name] = value
+
+    def ctype(decl, base, star, size):
+        if base in abi.structs:
+            t, pointer = abi.structs[base], C.POINTER(abi.structs[base])
+        elif base in _SCALARS:
+            t, pointer = _SCALARS[base], C.c_void_p
+        elif base in ("void", "char") or base in abi.opaque:
+            t, pointer = None, C.c_void_p
+        else:
+            raise GsrError(f"gsrast.h: unknown type {base!r} in {decl!r}")
+        t = pointer if star else t
+        if t is None:
+            raise GsrError(f"gsrast.h: {base!r} by value in {decl!r}")
+        if size is not None:
+            n = int(size) if size.isdigit() else abi.constants.get(size)
+            if n is None:
+                raise GsrError(f"gsrast.h: unknown array size {size!r} in {decl!r}")
+            t = t * n
+        return t
+
+    def declarations(decl, named):
+        """(name, ctypes type) of every declarator of `float *a, *b`, `float m1[9], m2[25]`, `const GsrView* views`, `GsrProfile*`.
+        named: a struct's fields (a name each, arrays allowed); else a parameter or a return type (no arrays)."""
+        decl = " ".join(decl.split())
+        head = _DECL.fullmatch(decl)
+        for d in head.group(2).split(",") if head else [""]:
+            m = _DECLARATOR.fullmatch(d)
+            if not head or not m or (not m.group(2) if named else m.group(3)):
+                raise GsrError(f"gsrast.h: cannot read the declaration {decl!r}")
+            yield m.group(2), ctype(decl, head.group(1), m.group(1), m.group(3))
+
+    def item(m):
+        if m["define"]:
+            lit = re.fullmatch(r"(\d+)u?", m["value"])
+            if not lit and m["value"] != "UINT64_MAX":
+                raise GsrError(f"gsrast.h: cannot read the value of {m[0].strip()!r}")
+            const(m["define"], int(lit.group(1)) if lit else 2 ** 64 - 1)
+        elif m["enum"] is not None:
+            block, value = {}, -1
+            for e in m["enum"].split(","):
+                em = re.fullmatch(r"\s*(\w+)\s*(?:=\s*(-?\d+)\s*)?", e)
+                if not em:
+                    raise GsrError(f"gsrast.h: cannot read the enumerator {e.strip()!r}")
+                value = int(em.group(2)) if em.group(2) else value + 1
+                const(em.group(1), value)
+                block[em.group(1)] = value
+            abi.enums.append(block)
+        elif m["opaque"]:
+            abi.opaque.add(m["opaque"])
+        elif m["struct"]:
+            fields = [f for d in m["fields"].split(";") if d.strip() for f in declarations(d, named=True)]
+            abi.structs[m["struct"]] = type(m["struct"], (C.Structure,), {"_fields_": fields})
+        else:
+            ret, params = " ".join(m["ret"].split()), m["params"].strip()
+            restype = None if ret == "void" else C.c_char_p if ret == "const char*" else next(declarations(ret, named=False))[1]
+            args = [a for p in params.split(",") for a in declarations(p, named=False)] if params not in ("", "void") else []
+            abi.symbols.append((m["fn"], restype, [pending.pop((m["fn"], name), t) for name, t in args]))
+        return ""
+
+    rest = [ln.strip() for ln in _ITEM.sub(item, re.sub(r"/\*.*?\*/", " ", text, flags=re.S)).splitlines() if ln.strip()]
+    if not _PREAMBLE.fullmatch(" ".join(" ".join(rest).split())):
+        stray = [ln for ln in rest if not re.fullmatch(r'#(ifndef|define|ifdef|endif|include)\b[^;]*|extern "C" \{|\}', ln)]
+        raise GsrError("gsrast.h: not understood: " + " | ".join(stray or rest))
+    if pending:
+        raise GsrError(f"gsrast.h declares no such function / parameter: {sorted(pending)}")
+    return abi
+
+
+# The one thing the header cannot say: these parameters point to HOST memory. They keep their element type, and ctypes
+# then refuses anything but a pointer to, or an array of, that type.
+_HOST_POINTERS = {
+    ("gsr_profile_collect", "ms"): C.POINTER(C.c_double),
+    ("gsr_profile_collect", "counts"): C.POINTER(C.c_int64),
+    ("gsr_forward_project", "n_pairs_host"): C.POINTER(C.c_uint64),
+    ("gsr_pack_views_streams", "streams"): C.POINTER(C.c_uint32),
+    ("gsr_photo_window", "taps"): C.POINTER(C.c_float),
+    ("gsr_extract_fields", "center"): C.POINTER(C.c_float),
+}
+
+with open(HEADER_PATH) as _fh:
+    _abi = parse_header(_fh.read(), _HOST_POINTERS)
+
+globals().update(_abi.constants)     # every GSR_* #define and enumerator: GSR_OK .. GSR_ESCRATCH, GSR_MAX_*, GSR_STAGE_*, ...
+SYMBOLS = _abi.symbols               # every function the header declares: (name, restype, argtypes)
+_S = _abi.structs
+GsrView, GsrModel, GsrScene = _S["GsrView"], _S["GsrModel"], _S["GsrScene"]
+GsrModelGrads, GsrSceneGrads, GsrGaussians = _S["GsrModelGrads"], _S["GsrSceneGrads"], _S["GsrGaussians"]
+GsrGeom, GsrBinning, GsrImages, GsrImageGrads = _S["GsrGeom"], _S["GsrBinning"], _S["GsrImages"], _S["GsrImageGrads"]
+GsrGrads, GsrAdamGroup, GsrRowRegion, GsrRowSet = _S["GsrGrads"], _S["GsrAdamGroup"], _S["GsrRowRegion"], _S["GsrRowSet"]
+GsrDispViews, GsrPlacement, GsrFrameViews = _S["GsrDispViews"], _S["GsrPlacement"], _S["GsrFrameViews"]
+GsrDensifyPlan, GsrDensifyTensor, GsrDensifyTable = _S["GsrDensifyPlan"], _S["GsrDensifyTensor"], _S["GsrDensifyTable"]
+GsrPhotoViews, GsrPhotoWeights = _S["GsrPhotoViews"], _S["GsrPhotoWeights"]
+if set(_S) - set(globals()):
+    raise GsrError(f"{__file__} binds no name to {sorted(set(_S) - set(globals()))} of gsrast.h")
+
+
+def _enum_names(prefix: str) -> list:
+    """The lower-cased suffixes of the enum whose enumerators start with `prefix`, in value order, without COUNT."""
+    block, = (e for e in _abi.enums if all(k.startswith(prefix) for k in e))
+    return [k[len(prefix):].lower() for k in sorted(block, key=block.get) if k != prefix + "COUNT"]
+
+
+STAGES = _enum_names("GSR_STAGE_")                    # "preprocess" .. "preprocess_bwd"
+GSR_DENSIFY_NAMES = tuple(_enum_names("GSR_DENSIFY_"))  # "xyz" .. "rotation": the order of GsrDensifyTable.t
+
+_lib = None
 
 
 def load() -> C.CDLL:
@@ -297,8 +173,8 @@ def load() -> C.CDLL:
             raise GsrError(f"{LIB_PATH} does not export {name} (declared in include/gsrast.h)") from e
         fn.restype = res
         fn.argtypes = args
-    if lib.gsr_version() != 1:
-        raise GsrError(f"libgsrast ABI version {lib.gsr_version()} != 1")
+    if lib.gsr_version() != GSR_VERSION:  # noqa: F821 (from the header)
+        raise GsrError(f"libgsrast ABI version {lib.gsr_version()} != {GSR_VERSION} of include/gsrast.h")  # noqa: F821
     _lib = lib
     return lib
 

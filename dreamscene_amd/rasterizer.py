@@ -542,7 +542,7 @@ def _forward_steps(s: GaussianRasterizationSettings, means3D, opacities, shs, co
             keep_bufs = (buf,)
             view_src = {k: (buf, offs[k]) for k in offs}
             if N >= (1 << 32):
-                L.check(-2, "gsr_forward_render")
+                L.check(L.GSR_ECAPACITY, "gsr_forward_render")
             if N > cap:
                 # speculation too small: redo binning + render exactly (projection results are still valid)
                 buf2, ptrs2, offs2 = alloc_state(N)

@@ -1,9 +1,11 @@
 """CPU: the C-ABI library builds for gfx950, loads, and exports every symbol include/gsrast.h declares (no compute
 calls: there is no GPU here). Also the host-side error behaviour of the drop-in Python interface."""
 import ctypes
+import functools
 import os
 import re
 import subprocess
+import tempfile
 
 import pytest
 import torch
@@ -109,26 +111,169 @@ def test_project_batch_rejects_several_views_beyond_256_tiles_before_touching_an
     assert geoms[0].sorted_idx is None and geoms[1].sorted_idx is None
 
 
-def test_struct_layouts_match_header(built_lib):
-    """ctypes mirrors of the POD structs have the sizes the C compiler gives them."""
+def _header_code():
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "gsrast.h")).read(), flags=re.S)
+
+
+def _binding_structs():
     from dreamscene_amd import _lib
-    src = r'''
-    #include <stdio.h>
-    #include "gsrast.h"
-    int main(){ printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(GsrView), sizeof(GsrGaussians), sizeof(GsrGeom),
-                       sizeof(GsrBinning), sizeof(GsrImages), sizeof(GsrImageGrads), sizeof(GsrGrads), sizeof(GsrRowRegion),
-                       sizeof(GsrRowSet)); return 0; }
-    '''
-    import tempfile
+    return {n: t for n, t in vars(_lib).items() if isinstance(t, type) and issubclass(t, ctypes.Structure)}
+
+
+def _binding_constants():
+    from dreamscene_amd import _lib
+    return {n: v for n, v in vars(_lib).items() if n.startswith("GSR_") and isinstance(v, int)}
+
+
+@functools.lru_cache(maxsize=None)
+def _compiler_view():
+    """What gcc makes of gsrast.h for every struct, field and constant the binding has: one generated C program (a name the
+    binding misread does not compile). -> ({struct: sizeof}, {(struct, field): (offsetof, sizeof)}, {constant: value})"""
+    lines = []
+    for s, t in _binding_structs().items():
+        lines.append(f'printf("S {s} %zu\\n", sizeof({s}));')
+        lines += [f'printf("F {s} {f} %zu %zu\\n", offsetof({s}, {f}), sizeof((({s}*)0)->{f}));' for f, _ in t._fields_]
+    for c in _binding_constants():
+        lines.append(f'printf("C {c} %llu\\n", (unsigned long long){c});' if c == "GSR_N_PENDING" else
+                     f'printf("C {c} %lld\\n", (long long){c});')
+    src = '#include <stdio.h>\n#include <stddef.h>\n#include "gsrast.h"\nint main(void) {\n' + "\n".join(lines) + "\nreturn 0; }\n"
     with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "s.c")
+        c, exe = os.path.join(d, "s.c"), os.path.join(d, "s")
         open(c, "w").write(src)
-        exe = os.path.join(d, "s")
         subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        sizes = [int(x) for x in subprocess.check_output([exe]).split()]
-    mine = [ctypes.sizeof(t) for t in (_lib.GsrView, _lib.GsrGaussians, _lib.GsrGeom, _lib.GsrBinning, _lib.GsrImages,
-                                       _lib.GsrImageGrads, _lib.GsrGrads, _lib.GsrRowRegion, _lib.GsrRowSet)]
-    assert sizes == mine
+        out = subprocess.check_output([exe], text=True)
+    sizes, fields, consts = {}, {}, {}
+    for kind, *w in (ln.split() for ln in out.splitlines()):
+        if kind == "S":
+            sizes[w[0]] = int(w[1])
+        elif kind == "F":
+            fields[w[0], w[1]] = (int(w[2]), int(w[3]))
+        else:
+            consts[w[0]] = int(w[1])
+    return sizes, fields, consts
+
+
+def test_struct_layouts_match_header(built_lib):
+    """Every ctypes structure of the binding has the size the C compiler gives the header's struct, and every field of it the
+    compiler's offset and size. The set of structs is the one a cruder reading of the header finds (none dropped)."""
+    structs = _binding_structs()
+    assert set(structs) == set(re.findall(r"typedef\s+struct\s+(\w+)\s*\{", _header_code())) and len(structs) == 22
+    sizes, fields, _ = _compiler_view()
+    assert sizes == {s: ctypes.sizeof(t) for s, t in structs.items()}
+    mine = {(s, f): (getattr(t, f).offset, getattr(t, f).size) for s, t in structs.items() for f, _ in t._fields_}
+    assert fields == mine, {k: (fields[k], mine[k]) for k in mine if fields[k] != mine[k]}
+
+
+def test_constants_match_header(built_lib):
+    """Every GSR_* #define and enumerator of the binding has the value the C compiler gives it, and the binding has every
+    GSR_* name that stands in the header's code (none dropped)."""
+    mine = _binding_constants()
+    assert set(mine) == set(re.findall(r"\bGSR_[A-Z0-9_]+\b", _header_code())) and len(mine) == 46
+    assert _compiler_view()[2] == mine
+    assert mine["GSR_N_PENDING"] == 2 ** 64 - 1 and mine["GSR_ESCRATCH"] == -4 and mine["GSR_NOISE_SHS"] == 2
+
+
+def test_derived_name_lists_follow_the_enums():
+    from dreamscene_amd import _lib
+    assert len(_lib.STAGES) == _lib.GSR_STAGE_COUNT and _lib.STAGES.index("render_bwd") == _lib.GSR_STAGE_RENDER_BWD
+    assert _lib.STAGES[0] == "preprocess" and "count" not in _lib.STAGES
+    assert _lib.GSR_DENSIFY_NAMES[_lib.GSR_DENSIFY_SCALING] == "scaling"
+    assert len(_lib.GSR_DENSIFY_NAMES) == _lib.GSR_DENSIFY_TENSORS
+    assert (_lib.GSR_OK, _lib.GSR_EINVAL, _lib.GSR_ECAPACITY, _lib.GSR_EHIP, _lib.GSR_ESCRATCH) == (0, -1, -2, -3, -4)
+
+
+# every construct of gsrast.h's grammar, small; %s takes what a case adds
+_TINY_HEADER = '''/* tiny.h -- a comment with a ; and a { in it */
+#ifndef TINY_H
+#define TINY_H
+#include <stddef.h>
+#include <stdint.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define GSR_N 3 /* trailing comment */
+#define GSR_FLAG 2u
+#define GSR_BIG UINT64_MAX
+enum {
+  GSR_A = -1, /* explicit */
+  GSR_B,
+  GSR_C = 5, GSR_D
+};
+enum { GSR_KIND_X, GSR_KIND_Y, GSR_KIND_COUNT };
+typedef struct GsrHandle GsrHandle;
+typedef struct GsrIn {
+  int32_t P, N;          /* several declarators */
+  float *a, *b;
+  const float* c;   uint8_t* d;    /* two declarations on one line */
+  float m1[9], m2[GSR_N];
+} GsrIn;
+typedef struct GsrOut { GsrIn in[GSR_N]; const GsrIn* ref; const void* p[2]; uint64_t seed; double y; size_t n; } GsrOut;
+%s
+GsrHandle* gsr_open(void);
+void gsr_close(GsrHandle*);
+const char* gsr_name(int code);
+size_t gsr_bytes(int32_t n, uint32_t m);
+int gsr_run(const GsrIn* in, GsrOut* out /* [n] */, double* ms, uint64_t n, float f, const uint8_t* mask,
+            void* stream, GsrHandle* h);
+#ifdef __cplusplus
+}
+#endif
+#endif /* TINY_H */
+'''
+
+
+def test_parser_reads_every_construct_of_the_grammar():
+    from dreamscene_amd._lib import parse_header
+    c = ctypes
+    abi = parse_header(_TINY_HEADER % "", {("gsr_run", "ms"): c.POINTER(c.c_double)})
+    assert abi.constants == dict(GSR_N=3, GSR_FLAG=2, GSR_BIG=2 ** 64 - 1, GSR_A=-1, GSR_B=0, GSR_C=5, GSR_D=6,
+                                 GSR_KIND_X=0, GSR_KIND_Y=1, GSR_KIND_COUNT=2)
+    assert abi.enums == [dict(GSR_A=-1, GSR_B=0, GSR_C=5, GSR_D=6), dict(GSR_KIND_X=0, GSR_KIND_Y=1, GSR_KIND_COUNT=2)]
+    assert list(abi.structs) == ["GsrIn", "GsrOut"]
+    In, Out = abi.structs["GsrIn"], abi.structs["GsrOut"]
+    assert issubclass(In, c.Structure) and In.__name__ == "GsrIn"
+    assert In._fields_ == [("P", c.c_int32), ("N", c.c_int32), ("a", c.c_void_p), ("b", c.c_void_p), ("c", c.c_void_p),
+                           ("d", c.c_void_p), ("m1", c.c_float * 9), ("m2", c.c_float * 3)]
+    assert Out._fields_ == [("in", In * 3), ("ref", c.POINTER(In)), ("p", c.c_void_p * 2), ("seed", c.c_uint64),
+                            ("y", c.c_double), ("n", c.c_size_t)]
+    assert abi.symbols == [
+        ("gsr_open", c.c_void_p, []),
+        ("gsr_close", None, [c.c_void_p]),
+        ("gsr_name", c.c_char_p, [c.c_int]),
+        ("gsr_bytes", c.c_size_t, [c.c_int32, c.c_uint32]),
+        ("gsr_run", c.c_int, [c.POINTER(In), c.POINTER(Out), c.POINTER(c.c_double), c.c_uint64, c.c_float, c.c_void_p,
+                              c.c_void_p, c.c_void_p])]
+    # without the exception the host pointer is a plain address like every other pointer
+    assert parse_header(_TINY_HEADER % "").symbols[4][2][2] is c.c_void_p
+
+
+@pytest.mark.parametrize("extra, quoted", [
+    ("typedef struct GsrCb { int32_t n; void (*cb)(int); } GsrCb;", "void (*cb)(int)"),       # function-pointer field
+    ("typedef struct GsrBits { int32_t a : 3; } GsrBits;", "int32_t a : 3"),                   # bit-field
+    ("typedef struct GsrU { int32_t n; foo_t x; } GsrU;", "foo_t"),                            # unknown type
+    ("typedef struct GsrArr { float m[GSR_NOPE]; } GsrArr;", "GSR_NOPE"),                      # undefined array size
+    ("int gsr_count = 3;", "int gsr_count = 3;"),                                              # stray statement
+    ("typedef struct GsrEarly { const GsrLate* p; } GsrEarly;\ntypedef struct GsrLate { int32_t n; } GsrLate;", "GsrLate"),
+    ("int gsr_arr(float center[3]);", "float center[3]"),                                      # array parameter
+    ("#define GSR_HALF 0.5", "GSR_HALF"),                                                      # not an integer
+    ("static int gsr_hidden(void);", "static"),                                                # a word left over
+    ("#define GSR_N 4", "GSR_N"),                                                              # defined twice
+], ids=["function_pointer", "bit_field", "unknown_type", "undefined_array_size", "stray_statement", "struct_before_definition",
+        "array_parameter", "non_integer_define", "leftover_word", "defined_twice"])
+def test_parser_refuses_what_it_does_not_recognise(extra, quoted):
+    """The same header with one thing outside the grammar: GsrError, and the message quotes the offending text."""
+    from dreamscene_amd._lib import GsrError, parse_header
+    with pytest.raises(GsrError) as e:
+        parse_header(_TINY_HEADER % extra)
+    assert quoted in str(e.value), str(e.value)
+
+
+@pytest.mark.parametrize("key", [("gsr_nope", "ms"), ("gsr_run", "nope")], ids=["no_such_function", "no_such_parameter"])
+def test_host_pointer_exception_must_name_a_declared_parameter(key):
+    from dreamscene_amd._lib import GsrError, parse_header
+    with pytest.raises(GsrError) as e:
+        parse_header(_TINY_HEADER % "", {key: ctypes.POINTER(ctypes.c_double)})
+    assert key[0] in str(e.value) and key[1] in str(e.value)
 
 
 def _build_c_caller(tmp, with_hip: bool) -> str:
