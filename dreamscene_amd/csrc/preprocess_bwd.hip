@@ -618,7 +618,8 @@ struct K8Views {
 //   B. the reached ones are listed in LDS (ballot / popcount prefix, ascending) and the four waves walk the list in rounds
 //      of 256 (wave slots rotated by the block index so that partial rounds do not pile up on one SIMD), running the dense
 //      chain rule on them -- same arithmetic, same summation order over the views, bit-identical rows -- and writing each
-//      row over the cleared one.
+//      row over the cleared one. (A row some view saw and no view reached is +0 here; the dense form's sigma_backward on an
+//      all-zero dSigma can leave -0 in it: equal values, tests/test_k8_blocks.py.)
 // Where a workgroup spends its time (tools/k8_stamps.py: realtime stamps inside the kernel; C3, 4 views, 489 workgroups of
 // 1 024 Gaussians, 161 of them reached on average, all resident at once; us since the workgroup's entry, mean):
 //   classified 14.5 | parameters + SH row in 27.6 | rows cleared 47.9 | views done 54.0 58.4 62.5 66.6 | rows stored 69.2
@@ -702,7 +703,7 @@ k_preprocess_bwd_views(const GsrView v, const GsrGaussians g, const K8Views vb, 
   // REACHED: the workgroup's 4 kPer chunks of 64 consecutive Gaussians lie gridDim.x * 64 apart -- how many Gaussians the
   // views reached varies along the index (C3: 161 of 1 024 on average, 566 in the densest contiguous block, 455 with four
   // slices of 256, and the kernel ends with the workgroup that has the most rounds); chunks from sixteen places average it.
-  // Chunk c = 4 t + wave belongs to the lanes of `wave` in slice t of phase A.
+  // Chunk c = 4 t + wave belongs to the lanes of `wave` in slice t of phase A. (tests/k8_layout.py restates this layout.)
   const auto chunk_base = [&](int c) { return ((int64_t)c * gridDim.x + blockIdx.x) * 64; };
   const int64_t first = REACHED ? chunk_base(0) : (int64_t)blockIdx.x * 256;
   int64_t i = first + tid;
@@ -1395,6 +1396,7 @@ struct K8Plan {
   bool restores_scratch, marks_every_row, big;
 };
 
+// (tests/k8_layout.py restates `big` and the launch grid that follows from it: change them together)
 static K8Plan k8_plan(int n_views, const GsrView& v, const GsrGaussians& g, const GsrGrads& out) {
   const bool sparse = gsr_k8_sparse() && v.sh_stride >= 9;
   K8Form f;

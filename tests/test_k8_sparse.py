@@ -1,14 +1,19 @@
-"""-m gpu: K8's sparse form (csrc/preprocess_bwd.hip, k_preprocess_bwd_views<K, PVS, REACHED>). A workgroup of 256
-Gaussians of which K7 reached at most 128 compacts them and runs the chain rule on those only; the others get zeros
-from coalesced clears. The scene below puts all three cases side by side -- workgroups nothing reached (opacity below
-1/255: visible, never blended), workgroups mostly reached (they stay dense) and mixed ones -- and the gradients are
-compared with the C oracle for single-view calls (write, then accumulate) and for one batched 4-view call."""
+"""-m gpu: K8's sparse form (csrc/preprocess_bwd.hip, k_preprocess_bwd_views<K, PVS, REACHED, KPER>). A workgroup owns 4 KPER
+chunks of 64 Gaussians that lie a grid's width apart (tests/k8_layout.py restates the layout; P = 2048 here: 8 workgroups of 4
+chunks). It lists the Gaussians K7 marked in LDS and walks the list in rounds of 256, one 64-entry slot per wave; a wave without
+entries writes the exchange bitmap and the visibility statistics and clears, chunk by chunk, the rows nothing reached. The scene
+below gives the workgroups, under the kernel's real layout, lists of every kind side by side -- nothing reached (opacity below
+1/255: visible, never blended), all 256 rows (no idle wave, nothing to clear), 224 (no idle wave at first), 128 and 64 (idle
+waves clear while busy ones run the chain rule), and 20 % candidates of which one workgroup's sit on the alpha threshold (the
+reached rows change with the cameras) -- and the gradients are compared with the C oracle for single-view calls (write, then
+accumulate) and for one batched 4-view call."""
 import os
 
 import numpy as np
 import pytest
 import torch
 
+from tests import k8_layout
 from tests.util import err, oracle_view, rel_scale, settings_for, small_scene
 
 pytestmark = pytest.mark.gpu
@@ -18,14 +23,28 @@ P, H, W, K, D = 2048, 80, 96, 16, 3
 
 
 def _scene():
+    """The cloud is thin (opacity 0.01 .. 0.04: no pixel saturates, so every row that may be blended IS reached by every view that
+    has it on screen) and which rows may be blended is set by workgroup: block b of tests/k8_layout.py, row index j."""
     g, _ = small_scene(P=P, H=H, W=W, K=K, seed=29, scale_mul=2.5)
-    op = g["opacities"].reshape(-1)
-    op[:768] = np.clip(op[:768], 0.05, 0.6)        # thin, translucent cloud: most of it is reached (dense workgroups)
-    op[768:1024:2] = 0.002                         # every other one of this workgroup can never pass alpha >= 1/255
-    op[1024:1536] = 0.003                          # two workgroups nothing reaches
-    op[1536:] = np.where(np.arange(512) % 5 == 0, op[1536:], 0.001)   # 20 % candidates: sparse workgroups
-    g["opacities"] = op.reshape(g["opacities"].shape).astype(np.float32)
+    op = np.clip(g["opacities"].reshape(-1), 0.01, 0.04)      # block 0: all 256 rows reached
+    blk, j = k8_layout.block_of_row(P, np.arange(P)), np.arange(P)
+    never = (((blk == 1) & (j % 4 != 0)) |                     # 64 reached, spread over the four chunks: one busy wave
+             ((blk == 2) & (j % 8 == 3)) |                     # 224: no idle wave until the list runs out
+             ((blk == 3) & (j % 2 == 0)) |                     # 128: two busy waves, two idle ones
+             (blk == 4) | (blk == 5) |                         # two workgroups nothing reaches
+             ((blk >= 6) & (j % 5 != 0)))                      # 20 % candidates
+    op[never] = np.where(blk[never] >= 4, 0.003, 0.002)       # can never pass alpha >= 1/255
+    op[(blk == 7) & ~never] = 0.003925                        # on the threshold (1/255 = 0.0039216): reached where a pixel centre
+    g["opacities"] = op.reshape(g["opacities"].shape).astype(np.float32)      # falls within ~0.04 sigma -- depends on the camera
     return g
+
+
+def assert_every_kind_of_block(reached):
+    """reached: bool [P] from the oracle. Under the kernel's layout there must be a workgroup nothing reached, one with all 256
+    rows reached (no idle wave, nothing to clear) and one with idle and busy waves side by side (1 .. 192 entries)."""
+    per_wg = k8_layout.reach_counts(reached, P)
+    assert per_wg.min() == 0 and per_wg.max() == 256 and ((per_wg > 0) & (per_wg <= 192)).any(), per_wg
+    return per_wg
 
 
 def _oracle_sum(c_oracle, g, cams, bg, ups):
@@ -59,8 +78,7 @@ def test_sparse_and_dense_workgroups_vs_oracle(built_lib, c_oracle):
     bg = np.array([0.1, 0.3, 0.9], np.float32)
     ups = [synth.upstream_grads(H, W, seed=k) for k in range(4)]
     ref, ref_m2, reached = _oracle_sum(c_oracle, g, cams, bg, ups)
-    per_wg = reached.reshape(-1, 256).sum(1)
-    assert per_wg.min() == 0 and per_wg.max() > 128 and ((per_wg > 0) & (per_wg <= 128)).any(), per_wg   # all three cases
+    assert_every_kind_of_block(reached)
     t = {k: torch.tensor(v, device=DEV) for k, v in g.items()}
     dev = torch.device(DEV)
     # (1) one call per view: the first writes the arena, the others accumulate into it
